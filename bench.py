@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """rays/s of the NeRF-SOS render path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 launches its own N ranks (re-exec under `python -m torch.distributed.run --nproc-per-node N
 --master-addr 127.0.0.1`); it is equally happy to be started by torch.distributed.run itself (RANK / LOCAL_RANK /
@@ -16,8 +16,13 @@ A step = one pass of the hot path over one synthetic batch already resident in H
       ONE flat RCCL all-gather of the patch tensors the batch-wide losses read, ONE flat all-reduce of the gradients.
   c5: configs[4] -- full-image eval 1008x756 in 65536-ray chunks, fp16 MFMA, rays generated on device, row blocks
       sharded over the GPUs, on-device post-processing; a step = one image.
-The default run also measures c3 / c5 / c4 (and the split-fp16 kernel) briefly, OUTSIDE the timed region, and reports
-them under "variants", each with its own roofline.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (metric, value, unit, ms_per_step, dtype, the
+roofline of the kernel launches inside the timed steps).  Everything that takes runs of its own is behind `--full`: the
+variants (c2: c3 / c5 / c4 and the split-fp16 kernel, briefly, OUTSIDE the timed region, each with its own roofline), the
+CPU baseline and parity tables, the graph-replayed steps, the step breakdowns, C5's quality renders and HBM rooflines, the
+16-bit kernels' clock probe; `--full` prints the whole record first ({"bench_detail": ...}, also ./bench_detail.json).
+`--dump-outputs DIR` writes what the last timed step computed (the arrays its caller receives) as DIR/<name>.npy, float32
+or float64, rank 0's only; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -800,7 +805,7 @@ def run_c2(ctx, args, precision="fp32", steps=None, warmup=None, blocks=1):
     # the same step replayed as ONE HIP graph (nerf_sos_amd.GraphedRender: the package's opt-in API for fixed-shape eval loops; its
     # outputs are static buffers, which is why NeRFNet.forward itself -- the timed headline -- stays eager): outside the timed region
     graphed = None
-    if ctx.world == 1 and blocks == 1:
+    if ctx.world == 1 and blocks == 1 and args.full:
         try:
             gr = nerf_sos_amd.GraphedRender(net, n_rays, (syn.NEAR, syn.FAR))
             for _ in range(3):
@@ -932,11 +937,15 @@ def run_patch_training(ctx, args, patches_per_gpu: int, precision: str, steps: i
     per_step = {k: round(v / (steps * blocks), 3) for k, v in sorted(sharding.reset_collective_counts().items())}
     n_rays = len(own) * PATCH * PATCH
     res = speed_fields(ctx, n_rays, steps, dt, per_rank)
+    if args.dump_outputs:    # the step's caller gets the loss and the updated trainable weights (later steps below move them on)
+        res["out"] = dict({"loss": state["loss"].detach().clone()},
+                          **{"param." + n_: p_.detach().clone() for n_, p_ in net.named_parameters() if p_.requires_grad})
     if blocks > 1:
         res["timing_blocks"] = blk
     peak = PEAK_FP32_MFMA_TFLOPS if precision == "fp32" else PEAK_16BIT_MFMA_TFLOPS
     kname = {"fp32": "mlp_fused_kernel<2,true,1>", "fp16x3": "mlp_x3_kernel<2,1>"}.get(precision, f"{lp_kernel_name()}<{precision},2,SAVE>")
-    roof = add_power_note(kernel_roofline(events, n_rays * N_FINE, MAC_SEMCOORD, peak, f"{kname} (fine pass of the rank's {n_rays} rays, {n_rays * N_FINE} points)"), precision, ctx, n_rays)
+    roof = add_power_note(kernel_roofline(events, n_rays * N_FINE, MAC_SEMCOORD, peak, f"{kname} (fine pass of the rank's {n_rays} rays, {n_rays * N_FINE} points)"),
+                          precision, ctx if args.full else None, n_rays)
     flop_per_ray = 2 * MAC_SEMCOORD * EVALS_PER_RAY
     if roof:
         roof["whole_step_frac_forward_flops_only"] = round(res["value"] / ctx.world * flop_per_ray / 1e12 / peak, 4)
@@ -944,6 +953,21 @@ def run_patch_training(ctx, args, patches_per_gpu: int, precision: str, steps: i
     def mean_ms(pairs):
         v = [a.elapsed_time(b) for a, b in pairs]
         return round(sum(v) / max(1, len(v)), 4)
+
+    st = timings.get("stats", {})
+    res.update(roofline=roof, whole_step_graph=None, rays_per_gpu=n_rays, patches=B, loss=round(float(state["loss"]), 6), precision=precision,
+               contrastive_loss=("NeRFContrastive on the batch's class tokens, weight 0.01" if contrast is not None else
+                                 "not evaluated: one patch has no off-diagonal similarity (the reference's argmin fails on B = 1)"),
+               collectives={"backend": ctx.backend, "all_gather_ms": mean_ms(timings.get("gather", [])),
+                            "all_reduce_ms": mean_ms(timings.get("allreduce", [])),
+                            "gathered_bytes_per_patch": st.get("bytes_per_patch"),
+                            "gathered_keys": list(sharding.PATCH_KEYS), "all_gathers_per_step": st.get("collectives", 0 if ctx.world == 1 else None),
+                            # every collective this rank issued in the timed steps, by kind (sharding.collective counts them): the
+                            # flat patch gather, the row-partitioned losses' two reductions (means, sums), the gradient all-reduce
+                            "calls_per_step_by_kind": per_step, "calls_per_step": round(sum(per_step.values()), 3),
+                            "all_reduce_floats": sum(p.numel() for p in net.parameters() if p.requires_grad)})
+    if not args.full:        # the graphed step and the diagnostic steps below are runs of their own
+        return res
 
     # The same step as ONE HIP graph (single process only: graphs.GraphedPatchStep -- device-side Philox counter, loss generator
     # registered with the graph, capturable fused Adam; bit-identical to the eager step, tests/test_gpu_configs.py): one
@@ -1006,22 +1030,10 @@ def run_patch_training(ctx, args, patches_per_gpu: int, precision: str, steps: i
                    "calls": len(v) // 3} for k, v in sorted(coll_ev.items())}
     breakdown = {k: mean_ms(diag_t.get(k, [])) for k in ("render", "gather", "losses_backward", "allreduce")}
     breakdown["optimizer"] = mean_ms(opt_ev)
-    st = timings.get("stats", {})
     res.update(step_breakdown_ms=dict(breakdown, what="HIP-event spans on rank 0's stream, mean of 3 eager steps outside the timed regions: train-mode "
                                                       "render of the own patches | flat patch all-gather | losses + backward (N > 1: with the two loss "
                                                       "reductions inside) | flat gradient all-reduce | fused Adam"),
-               collective_ms_by_kind=by_kind)
-    res.update(roofline=roof, whole_step_graph=graph, rays_per_gpu=n_rays, patches=B, loss=round(float(state["loss"]), 6), precision=precision,
-               contrastive_loss=("NeRFContrastive on the batch's class tokens, weight 0.01" if contrast is not None else
-                                 "not evaluated: one patch has no off-diagonal similarity (the reference's argmin fails on B = 1)"),
-               collectives={"backend": ctx.backend, "all_gather_ms": mean_ms(timings.get("gather", [])),
-                            "all_reduce_ms": mean_ms(timings.get("allreduce", [])),
-                            "gathered_bytes_per_patch": st.get("bytes_per_patch"),
-                            "gathered_keys": list(sharding.PATCH_KEYS), "all_gathers_per_step": st.get("collectives", 0 if ctx.world == 1 else None),
-                            # every collective this rank issued in the timed steps, by kind (sharding.collective counts them): the
-                            # flat patch gather, the row-partitioned losses' two reductions (means, sums), the gradient all-reduce
-                            "calls_per_step_by_kind": per_step, "calls_per_step": round(sum(per_step.values()), 3),
-                            "all_reduce_floats": sum(p.numel() for p in net.parameters() if p.requires_grad)})
+               collective_ms_by_kind=by_kind, whole_step_graph=graph)
     return res
 
 
@@ -1051,6 +1063,8 @@ def run_c5(ctx, args, precision: str, steps: int, warmup: int, blocks: int = 1, 
     dt, per_rank, events, blk = timed_blocks(ctx, step, warmup, steps, blocks)
     n_rays = e - s
     res = speed_fields(ctx, n_rays, steps, dt, per_rank)
+    if args.dump_outputs:
+        res["out"] = dict(state["post"], rgb=state["rgb"])
     if blocks > 1:
         res["timing_blocks"] = blk
     # the total over ranks is the image, not world x the first rank's block
@@ -1058,7 +1072,8 @@ def run_c5(ctx, args, precision: str, steps: int, warmup: int, blocks: int = 1, 
     peak = PEAK_FP32_MFMA_TFLOPS if precision == "fp32" else PEAK_16BIT_MFMA_TFLOPS
     full_chunk = min(chunk, n_rays)
     roof = add_power_note(kernel_roofline(events, full_chunk * N_FINE, MAC_SEMCOORD, peak,
-                                          f"{lp_kernel_name()}<{precision},2> (fine pass of a {full_chunk}-ray chunk, {full_chunk * N_FINE} points)"), precision, ctx, full_chunk)
+                                          f"{lp_kernel_name()}<{precision},2> (fine pass of a {full_chunk}-ray chunk, {full_chunk * N_FINE} points)"),
+                          precision, ctx if args.full else None, full_chunk)
     flop_per_ray = 2 * MAC_SEMCOORD * EVALS_PER_RAY
     if roof:
         roof["whole_path_frac"] = round(res["value"] / ctx.world * flop_per_ray / 1e12 / peak, 4)
@@ -1066,7 +1081,7 @@ def run_c5(ctx, args, precision: str, steps: int, warmup: int, blocks: int = 1, 
     # weights with the sigma head x40, -1.5: the default-init field is empty and its PSNR says nothing) in this precision and
     # through the exact-fp32 kernels (= the reference within 1e-4, tests/test_gpu_parity.py); outside the timed region
     quality = None
-    if precision != "fp32" and ctx.rank == 0:
+    if precision != "fp32" and ctx.rank == 0 and args.full:
         rays = syn.image_rays(ctx.dev, (s, min(s + chunk, e)))
         field = make_dense_field(net, rays, (syn.NEAR, syn.FAR))
         with torch.no_grad():
@@ -1083,7 +1098,7 @@ def run_c5(ctx, args, precision: str, steps: int, warmup: int, blocks: int = 1, 
                        "what": f"{rays.shape[1]} rays of the image through a dense field, {precision} vs the exact-fp32 kernels"}
     res.update(roofline=roof, rays_per_gpu=n_rays, precision=precision, coarse_precision=coarse, image=f"{syn.W}x{syn.H}", chunk=chunk,
                finite=bool(torch.isfinite(state["rgb"]).all().item()), quality_dense_random_field=quality)
-    if ctx.rank == 0:
+    if ctx.rank == 0 and args.full:
         del net
         torch.cuda.empty_cache()
         if precision != "fp32":
@@ -1194,6 +1209,32 @@ def _strip(res):
     return {k: v for k, v in res.items() if k not in ("out", "net", "rays") and not (k == "replayed_as_hip_graph" and v is None)}
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6 - (1 << 16)     # --dump-outputs: every file together under 64 MB, .npy headers included
+
+
+def dump_outputs(ctx, args, arrays):
+    """`--dump-outputs DIR`: rank 0 writes every tensor of `arrays` (what the last timed step handed its caller) as DIR/<name>.npy,
+    float64 where the tensor is float64 or integer, float32 otherwise; empty tensors are left out.  Over the budget, every array
+    keeps the same seeded sample of its leading dimension (numpy default_rng(0), rows in order), so files of two builds line up."""
+    if not args.dump_outputs or ctx.rank != 0 or not arrays:
+        return
+    import numpy as np
+    torch = ctx.torch
+    host = {}
+    for name, t in arrays.items():
+        if not torch.is_tensor(t) or t.numel() == 0:
+            continue
+        exact = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        host[name] = t.detach().to("cpu", torch.float64 if exact else torch.float32).numpy()
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_BUDGET_BYTES and a.ndim >= 1:
+            keep = max(1, int(a.shape[0] * DUMP_BUDGET_BYTES / total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
+
 # ---------------------------------------------------------------------------------------------------------------- main
 def run_generic_paths(ctx, rays_n: int = 4096, steps: int = 10):
     """The paths no BASELINE config names but the drop-in contract includes, timed briefly on the generic fp32 kernels (csrc/mlp_generic.hip):
@@ -1273,6 +1314,11 @@ def main():
                     help="c5 only: NeRFNet.coarse_precision (the coarse pass's arithmetic; default: the same as --precision)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-variants", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: variants, CPU baseline and parity, graph replay, "
+                         "step breakdowns, quality renders, per-kernel probes; prints the full record before the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
     _self_launch(args)
 
@@ -1290,6 +1336,7 @@ def main():
         if prec != "fp32":
             raise SystemExit("bench.py: c1 is the reference's own fp32 CPU case: --precision fp32")
         res = run_c1(ctx, args)
+        dump_outputs(ctx, args, res["out"])
         line.update({k: res[k] for k in ("value", "ms_per_step", "host_enqueue_ms_per_step", "per_rank_rays_per_s")})
         line["metric"] = "rays/sec (coarse only, 64 samples)"
         line["dtype"] = "f32"
@@ -1301,6 +1348,7 @@ def main():
         if prec not in ("fp32", "fp16x3"):
             raise SystemExit("bench.py: c2 is the fp32 configuration: --precision fp32 (exact) or fp16x3 (split-fp16, fp32-grade)")
         res = run_c2(ctx, args, prec)
+        dump_outputs(ctx, args, res["out"])
         roof = res["roofline"]
         add_traffic(roof, "c2_fp32" if prec == "fp32" else "c2_fp16x3")
         line.update({k: res[k] for k in ("value", "ms_per_step", "host_enqueue_ms_per_step", "per_rank_rays_per_s")})
@@ -1313,7 +1361,7 @@ def main():
                           "flop_per_ray": res["flop_per_ray"]}
         line["roofline"] = roof
         line["replayed_as_hip_graph"] = res.get("replayed_as_hip_graph")
-        if not args.no_variants:
+        if args.full and not args.no_variants:
             vsteps = max(3, min(args.steps, 20))      # the variants ride along briefly, outside the headline's timed region
             if ctx.world == 1 and prec == "fp32":
                 exact_c = res["out"]["rgb0"]
@@ -1348,7 +1396,9 @@ def main():
     elif args.config in ("c3", "c4"):
         if args.config == "c3" and ctx.world != 1:
             raise SystemExit("bench.py: c3 is the single-GPU configuration; the sharded one is c4")
-        res = _strip(run_patch_training(ctx, args, 1 if args.config == "c3" else 2, prec, args.steps, args.warmup))
+        res = run_patch_training(ctx, args, 1 if args.config == "c3" else 2, prec, args.steps, args.warmup)
+        dump_outputs(ctx, args, res.get("out"))
+        res = _strip(res)
         line.update({k: res[k] for k in ("value", "ms_per_step", "host_enqueue_ms_per_step", "per_rank_rays_per_s")})
         line["dtype"] = {"fp32": "f32", "fp16x3": "f16x3"}.get(prec, prec)
         line["config"] = {"workload": ("BASELINE configs[2]: 4096 rays = one 64x64 patch" if args.config == "c3" else
@@ -1367,7 +1417,9 @@ def main():
         line["whole_step_graph"] = res.get("whole_step_graph")
         line["contrastive_loss"] = res.get("contrastive_loss")
     else:
-        res = _strip(run_c5(ctx, args, prec, args.steps, args.warmup, coarse=args.coarse_precision))
+        res = run_c5(ctx, args, prec, args.steps, args.warmup, coarse=args.coarse_precision)
+        dump_outputs(ctx, args, res.get("out"))
+        res = _strip(res)
         line.update({k: res[k] for k in ("value", "ms_per_step", "host_enqueue_ms_per_step", "per_rank_rays_per_s")})
         line["scaling"] = "strong"
         line["dtype"] = {"fp32": "f32", "fp16x3": "f16x3"}.get(prec, prec)
@@ -1383,12 +1435,12 @@ def main():
     if variants:
         line["variants"] = variants
     if ctx.rank == 0:
-        if ctx.world == 1 and not args.no_cpu_baseline and args.config == "c1":
+        if args.full and ctx.world == 1 and not args.no_cpu_baseline and args.config == "c1":
             net = res["net"]
             line["cpu_baseline"], line["parity"] = cpu_baseline_c1(({k: v.detach().clone() for k, v in net.state_dict().items()}, res["rays"], res["out"]))
             for k in ("net", "rays", "out"):
                 res.pop(k, None)
-        if ctx.world == 1 and not args.no_cpu_baseline and args.config == "c2":
+        if args.full and ctx.world == 1 and not args.no_cpu_baseline and args.config == "c2":
             gpu = dense = None
             if prec in ("fp32", "fp16x3"):
                 net = res["net"]
@@ -1407,16 +1459,20 @@ def main():
                     del net, gpu, dense
                     torch.cuda.empty_cache()
                     parity["trained_field"] = trained_field_parity(torch, ctx.dev)
-        # The driver keeps the last 8 KB of stdout: the FULL record goes out first (one line, {"bench_detail": ...}, and
-        # ./bench_detail.json), then the line the contract asks for -- every headline field, every variant's value / ms / roofline,
-        # the parity summaries -- kept under 6 KB so that it survives whole.
-        print(json.dumps({"bench_detail": line}), flush=True)
-        try:
-            with open(os.path.join(os.getcwd(), "bench_detail.json"), "w") as f:
-                json.dump(line, f, indent=1)
-        except OSError:
-            pass
-        print(json.dumps(compact_line(line)), flush=True)
+        # The driver keeps the last 8 KB of stdout: with --full the FULL record goes out first (one line, {"bench_detail": ...},
+        # and ./bench_detail.json), then the line the contract asks for -- every headline field, every variant's value / ms /
+        # roofline, the parity summaries -- kept under 6 KB so that it survives whole.
+        compact = compact_line(line)
+        if args.full:
+            print(json.dumps({"bench_detail": line}), flush=True)
+            try:
+                with open(os.path.join(os.getcwd(), "bench_detail.json"), "w") as f:
+                    json.dump(line, f, indent=1)
+            except OSError:
+                pass
+        else:
+            compact["detail"] = "variants, CPU baseline, parity and the full tables: bench.py --full"
+        print(json.dumps(compact), flush=True)
     if ctx.world > 1:
         ctx.dist.barrier()
         ctx.dist.destroy_process_group()

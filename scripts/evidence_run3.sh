@@ -6,10 +6,10 @@ set -x
 O=gpurun_out/r03ev3; mkdir -p $O
 python -m pytest tests -m gpu -q > $O/b_gpu_tests.log 2>&1; tail -3 $O/b_gpu_tests.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/b_smoke.log 2>&1; tail -1 $O/b_smoke.log
-python bench.py > $O/i_bench_default_final.json 2> $O/i_bench_default_final.err
-python bench.py --config c3 --steps 30 --warmup 5 > $O/e_bench_c3.json 2>/dev/null
-python bench.py --config c4 --steps 30 --warmup 5 > $O/e_bench_c4.json 2>/dev/null
-python bench.py --config c5 --steps 3 --warmup 1 > $O/e_bench_c5.json 2>/dev/null
+python bench.py --full > $O/i_bench_default_final.json 2> $O/i_bench_default_final.err
+python bench.py --full --config c3 --steps 30 --warmup 5 > $O/e_bench_c3.json 2>/dev/null
+python bench.py --full --config c4 --steps 30 --warmup 5 > $O/e_bench_c4.json 2>/dev/null
+python bench.py --full --config c5 --steps 3 --warmup 1 > $O/e_bench_c5.json 2>/dev/null
 python scripts/bench_full_train.py 4096 fp16x3 > $O/e_bench_full_train.json 2>/dev/null
 python scripts/diag/graph_step_time.py > $O/d_graph_step_time.txt 2>&1
 (python scripts/diag/geo_fuse_time.py; python scripts/diag/wgrad_time.py 4096; python scripts/diag/wgrad_time.py 8192) > $O/k_loss_and_head_gradient_kernels.txt 2>&1

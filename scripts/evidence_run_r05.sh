@@ -27,11 +27,11 @@ if [ $STAGE = kernels ]; then
 else
     python -m pytest tests -m gpu -q > $O/b_gpu_tests.log 2>&1; tail -3 $O/b_gpu_tests.log
     python -c "import __graft_entry__ as g; g.smoke()" > $O/b_smoke.log 2>&1; tail -1 $O/b_smoke.log
-    python bench.py > $O/i_bench_default.out 2> $O/i_bench_default.err
-    python bench.py --config c1 > $O/e_bench_c1.out 2>/dev/null
-    python bench.py --config c3 --steps 30 --warmup 5 > $O/e_bench_c3.out 2>/dev/null
-    python bench.py --config c4 --steps 30 --warmup 5 > $O/e_bench_c4.out 2>/dev/null
-    python bench.py --config c5 --steps 3 --warmup 1 > $O/e_bench_c5.out 2>/dev/null
+    python bench.py --full > $O/i_bench_default.out 2> $O/i_bench_default.err
+    python bench.py --full --config c1 > $O/e_bench_c1.out 2>/dev/null
+    python bench.py --full --config c3 --steps 30 --warmup 5 > $O/e_bench_c3.out 2>/dev/null
+    python bench.py --full --config c4 --steps 30 --warmup 5 > $O/e_bench_c4.out 2>/dev/null
+    python bench.py --full --config c5 --steps 3 --warmup 1 > $O/e_bench_c5.out 2>/dev/null
     python scripts/bench_full_train.py 4096 fp16x3 > $O/e_bench_full_train.json 2>/dev/null
     python scripts/diag/generic_time.py > $O/l_generic_kernel_times.txt 2>&1
     python scripts/bench_generic_train.py > $O/m_generic_train.txt 2>&1
@@ -40,10 +40,10 @@ else
     python scripts/diag/graph_step_time.py > $O/d_graph_step_time.txt 2>&1
     python scripts/soak_determinism.py 100 2048 > $O/j_soak_determinism.txt 2>&1
     cd /tmp
-    rocprofv3 --kernel-trace --stats -d $R/$O/deftrace -o t --output-format csv -- python $R/bench.py --no-cpu-baseline --no-variants > $R/$O/deftrace.log 2>&1
+    rocprofv3 --kernel-trace --stats -d $R/$O/deftrace -o t --output-format csv -- python $R/bench.py --full --no-cpu-baseline --no-variants > $R/$O/deftrace.log 2>&1
     rocprofv3 --kernel-trace --stats -d $R/$O/c3trace -o t --output-format csv -- python $R/scripts/diag/graph_step_time.py 1 1 0 > $R/$O/c3trace.log 2>&1
     rocprofv3 --kernel-trace --stats -d $R/$O/c4trace -o t --output-format csv -- python $R/scripts/diag/graph_step_time.py 2 1 0 > $R/$O/c4trace.log 2>&1
-    rocprofv3 --kernel-trace --stats -d $R/$O/c5trace -o t --output-format csv -- python $R/bench.py --config c5 --steps 2 --warmup 1 --no-cpu-baseline > $R/$O/c5trace.log 2>&1
+    rocprofv3 --kernel-trace --stats -d $R/$O/c5trace -o t --output-format csv -- python $R/bench.py --full --config c5 --steps 2 --warmup 1 --no-cpu-baseline > $R/$O/c5trace.log 2>&1
     rocprofv3 --kernel-trace --stats -d $R/$O/posetrace -o t --output-format csv -- python $R/scripts/diag/raygrad_time.py > $R/$O/posetrace.log 2>&1
     cd $R
     cp $(find $O/deftrace -name "*kernel_stats.csv" | head -1) $O/f_kernel_stats_default_bench_no_variants.csv

@@ -346,3 +346,34 @@ def test_density_export_grid(manifest, cfg):
     net.mlp_precision = "fp32"
     with pytest.raises(ValueError):
         net.mlp_precision = "fp8"
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` (the headline, C2): ONE JSON line with the headline fields and none of what --full
+    adds; `--dump-outputs DIR` writes the last timed step's render as float .npy files, bit for bit the same from run to run."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], cwd=tmp_path, capture_output=True, text=True, timeout=800)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["dtype"] == "f32" and line["unit"] == "rays/s" and line["higher_is_better"] is True
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and line["metric"].startswith("rays/sec")
+        assert not {"variants", "cpu_baseline", "parity", "replayed_as_hip_graph"} & set(line), sorted(line)
+        assert not (tmp_path / "bench_detail.json").exists()
+        arrays = {p.name[:-4]: np.load(p) for p in d.iterdir()}
+        assert {"rgb", "depth", "acc", "rgb0", "depth0", "acc0"} <= set(arrays), sorted(arrays)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 * 10**6
+        assert arrays["rgb"].shape == (4096, 3) and np.isfinite(arrays["rgb"]).all()
+        outs.append(arrays)
+    for k, a in outs[0].items():
+        assert np.array_equal(a, outs[1][k]), k

@@ -147,7 +147,7 @@ def test_two_ranks_over_rccl():
 
 
 def _bench_lines(r):
-    """bench.py prints the full record first ({"bench_detail": ...}) and the contract's ONE line last, kept under 6 KB so that it
+    """bench.py --full prints the full record first ({"bench_detail": ...}) and the contract's ONE line last, kept under 6 KB so that it
     survives the driver's 8 KB stdout tail whole (VERDICT r04 #5).  Returns (detail, line)."""
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 2, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
@@ -169,7 +169,7 @@ def test_bench_launches_its_own_ranks():
     if torch.cuda.device_count() < 2:
         env["NSOS_BENCH_SHARE_GPU"] = "1"
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=800)
     j, line = _bench_lines(r)
     assert line["n_gpus"] == 2 and line["distributed"]["ranks_seen_by_collective"] == 2 and line["value"] == j["value"]
@@ -199,7 +199,7 @@ def test_bench_eight_ranks_smoke(config, steps):
         env.pop(k, None)
     env["NSOS_COLLECTIVE_TIMEOUT_S"] = "240"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--config", config, "--steps", str(steps),
-                        "--warmup", "1", "--no-variants"], env=env, capture_output=True, text=True, timeout=1400)
+                        "--warmup", "1", "--no-variants", "--full"], env=env, capture_output=True, text=True, timeout=1400)
     j, line = _bench_lines(r)
     assert line["n_gpus"] == 8 and line["value"] == j["value"]
     assert j["n_gpus"] == 8 and j["distributed"]["ranks_seen_by_collective"] == 8 and j["value"] > 0

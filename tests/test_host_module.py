@@ -126,6 +126,41 @@ def test_bench_self_launch_command(monkeypatch):
     assert not seen
 
 
+def test_bench_dump_outputs_types_and_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: one .npy per output, float32 (float64 for float64 and integer outputs), empty outputs left
+    out, rank 0 only; over the size budget every array keeps the same seeded rows, so two builds' files line up row for row."""
+    import importlib.util
+    import os
+    import types
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_module3", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rgb, sem, prob = torch.rand(1000, 3), torch.arange(1000, dtype=torch.int32), torch.rand(1000, 2).half()
+    arrays = {"rgb": rgb, "sem": sem, "prob": prob, "loss": torch.tensor(1.5, dtype=torch.float64), "semantics": torch.zeros(1000, 0)}
+    ctx = types.SimpleNamespace(torch=torch, rank=0)
+    bench.dump_outputs(ctx, types.SimpleNamespace(dump_outputs=str(tmp_path / "a")), arrays)
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(a) == ["loss", "prob", "rgb", "sem"]
+    assert a["rgb"].dtype == np.float32 and np.array_equal(a["rgb"], rgb.numpy())
+    assert a["sem"].dtype == np.float64 and np.array_equal(a["sem"], np.arange(1000))
+    assert a["prob"].dtype == np.float32 and np.array_equal(a["prob"], prob.float().numpy())
+    assert a["loss"].dtype == np.float64 and a["loss"].shape == () and a["loss"] == 1.5
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8000)
+    for run in ("b", "c"):
+        bench.dump_outputs(ctx, types.SimpleNamespace(dump_outputs=str(tmp_path / run)), arrays)
+    b = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    rows = b["sem"].astype(np.int64)                    # sem = row index: the rows kept
+    assert 0 < len(rows) < 1000 and (np.diff(rows) > 0).all() and sum(x.nbytes for x in b.values()) <= 8000
+    assert np.array_equal(b["rgb"], rgb.numpy()[rows]) and np.array_equal(b["prob"], prob.float().numpy()[rows]) and b["loss"] == 1.5
+    for f in os.listdir(tmp_path / "b"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)), f
+    ctx.rank = 1
+    bench.dump_outputs(ctx, types.SimpleNamespace(dump_outputs=str(tmp_path / "d")), arrays)
+    assert not os.path.exists(tmp_path / "d")
+
+
 class _FakePlan:
     """Stands in for ops.PackPlan on a machine without a GPU: counts the pack launches it would issue."""
     runs = 0

@@ -106,6 +106,13 @@ def neg_index(sim_matrix: torch.Tensor) -> torch.Tensor:
     return torch.min(sim_matrix, dim=0)[1]
 
 
+def super_perm(perm: torch.Tensor) -> torch.Tensor:
+    """utils/image.py:306-309 after its randperm draw `perm` (the negatives when sim_matrix is None): no patch is its own."""
+    perm = perm.clone()
+    perm[perm == torch.arange(perm.numel(), device=perm.device)] += 1
+    return perm % perm.numel()
+
+
 def correlation_loss(orig_feats, orig_code, neg_indx, coords1, coords2, p: CorrParams):
     """CorrelationLoss.forward (utils/image.py:335-370) with the random draws and the negative index injected."""
     feats = _sample(orig_feats, coords1)

@@ -188,3 +188,56 @@ def test_split_fp16_entry_points_validate_without_a_gpu():
     assert lib.nsos_wgrad_x3(p, 256, p, 256, 64, None, 256, None, p, 1 << 30, None) == -1          # dW NULL
     assert lib.nsos_wgrad_x3(p, 255, p, 256, 64, p, 256, None, p, 1 << 30, None) == -2             # row stride < 256
     assert lib.nsos_wgrad_x3(p, 256, p, 256, 64, p, 256, None, p, 1024, None) == -4                # workspace too small
+
+
+def test_loss_entry_points_refuse_out_of_range_shapes_and_write_nothing():
+    """The correlation-loss limits -- geo N = H W <= 4096 (the LDS-resident patch), code width C in 1..4 (kMaxC), appearance
+    S <= 32 (S^2 <= 1024) -- are enforced before any launch: every entry returns NSOS_ERR_UNSUPPORTED and leaves the loss and
+    gradient buffers as they were (host sentinels here: nothing on the device is reached)."""
+    import numpy as np
+    lib = _lib.lib()
+    UNSUPPORTED = -3
+    ws = np.zeros(64, np.float64)                 # 16-byte aligned, never touched
+    arg = C.c_void_p(ws.ctypes.data)
+    for case in ("geo", "geo_rows", "geo_pair", "app", "app_nhwc", "app_rows"):
+        for C_, shape in ((2, (1, 4097)), (2, (17, 241)), (0, (8, 8)), (5, (8, 8)), (2, (33,)), (0, (33,)), (5, (11,))):
+            geo = case.startswith("geo")
+            if geo != (len(shape) == 2):
+                continue
+            loss = np.full(1, 1234.5, np.float32)
+            grad = np.full(256, -7.25, np.float32)
+            grad1 = np.full(256, -7.25, np.float32)
+            L, G, G1 = (C.c_void_p(a.ctypes.data) for a in (loss, grad, grad1))
+            rows = np.zeros(2, np.int32)
+            R = C.c_void_p(rows.ctypes.data)
+            big = 1 << 40
+            if geo:
+                H, W = shape
+                if case == "geo":
+                    rc = lib.nsos_geo_correlation_loss(arg, arg, arg, arg, arg, 2, C_, H, W, 0.5, 1, 3, 1, 15, 1, L, G, arg, big, None)
+                elif case == "geo_rows":
+                    rc = lib.nsos_geo_correlation_loss_rows(3, arg, arg, arg, arg, arg, R, 2, 2, C_, H, W, 0.5, 1, 3, 1, 15, 1, L, G, arg,
+                                                            big, None, None, None)
+                else:
+                    rc = lib.nsos_geo_correlation_loss_pair(3, arg, arg, arg, arg, arg, arg, R, 2, 1, 0, C_, H, W, 0.5, 1, 3, 1, 15, L, G,
+                                                            G1, arg, big, None, None, None)
+            else:
+                (S,) = shape
+                if case == "app":
+                    rc = lib.nsos_app_correlation_loss(arg, arg, arg, arg, arg, 2, 7, 5, 3, C_, 13, 20, S, 0.18, 1, 0.46, 1, L, G, arg, big, None)
+                elif case == "app_nhwc":
+                    rc = lib.nsos_app_correlation_loss_nhwc(arg, arg, arg, arg, arg, 2, 7, 5, 3, C_, 13, 20, S, 0.18, 1, 0.46, 1, L, G, arg, big,
+                                                            None)
+                else:
+                    rc = lib.nsos_app_correlation_loss_rows(2, arg, arg, arg, arg, arg, R, 2, 2, 0, 7, 5, 3, C_, 13, 20, S, 0.18, 1, 0.46, 1, L,
+                                                            G, arg, big, None, None, None)
+            assert rc == UNSUPPORTED, (case, C_, shape, rc)
+            assert loss[0] == 1234.5 and (grad == -7.25).all() and (grad1 == -7.25).all(), (case, C_, shape)
+            assert (ws == 0).all()
+    assert b"specialised" in lib.nsos_error_string(UNSUPPORTED)
+    # the accepted boundary passes validation (and then stops at the buffer size: no launch either)
+    loss = np.full(1, 1234.5, np.float32)
+    L = C.c_void_p(loss.ctypes.data)
+    assert lib.nsos_geo_correlation_loss(arg, arg, arg, arg, arg, 1, 4, 32, 128, 0.5, 1, 3, 1, 15, 1, L, None, arg, 32, None) == -4
+    assert lib.nsos_app_correlation_loss(arg, arg, arg, arg, arg, 1, 7, 5, 3, 1, 13, 20, 32, 0.18, 1, 0.46, 1, L, None, arg, 32, None) == -4
+    assert loss[0] == 1234.5

@@ -47,6 +47,73 @@ def test_geo_correlation_loss_port():
     assert np.abs(code.grad.numpy() - g).max() <= 1e-6 * np.abs(g).max()
 
 
+EDGE = np.load(os.path.join(os.path.dirname(__file__), "golden", "losses_edges.npz"))
+EDGE_APP = sorted(k[:-6] for k in EDGE.files if k.endswith("_feats"))
+EDGE_GEO = sorted(k[:-6] for k in EDGE.files if k.endswith("_depth"))
+e = lambda k: torch.from_numpy(EDGE[k])  # noqa: E731
+
+
+def _edge_neg(tag):
+    """The negatives the reference used: the column arg-min of sim_matrix, or super_perm of the recorded randperm draw."""
+    B = EDGE[f"{tag}_code"].shape[0]
+    neg = lp.neg_index(e(f"{tag}_sim")) if f"{tag}_sim" in EDGE.files else lp.super_perm(e(f"{tag}_perm"))
+    assert np.array_equal(neg.numpy(), EDGE[f"{tag}_neg"]) and neg.shape == (B,)
+    if f"{tag}_sim" not in EDGE.files:
+        assert sorted(EDGE[f"{tag}_perm"].tolist()) == list(range(B))
+        assert B == 1 or (neg != torch.arange(B)).all()          # super_perm never pairs a patch with itself
+    return neg
+
+
+def test_edge_goldens_cover_the_issue_axes():
+    """losses_edges.npz reaches what losses.npz does not: code widths 1, 3, 4; S != 11 up to 32; Cf below 2 * kMaxC and odd;
+    non-square and one-pixel maps; ragged N; B in {1, 2, 5}; super_perm negatives; a whole patch beyond max_depth."""
+    widths = {EDGE[f"{t}_code"].shape[1] for t in EDGE_APP} & {EDGE[f"{t}_code"].shape[1] for t in EDGE_GEO}
+    assert {1, 3, 4} <= widths
+    S = {EDGE[f"{t}_rand1"].shape[1] for t in EDGE_APP}
+    assert 32 in S and len(S - {11}) >= 3
+    Cf = {EDGE[f"{t}_feats"].shape[1] for t in EDGE_APP}
+    assert {3, 7} <= Cf and any(c > 8 and c % 2 for c in Cf)
+    assert any(1 in EDGE[f"{t}_code"].shape[2:] for t in EDGE_APP) and any(1 in EDGE[f"{t}_code"].shape[2:] for t in EDGE_GEO)
+    assert any(EDGE[f"{t}_code"].shape[2] != EDGE[f"{t}_code"].shape[3] for t in EDGE_GEO)
+    Ns = [EDGE[f"{t}_depth"].shape[2] * EDGE[f"{t}_depth"].shape[3] for t in EDGE_GEO]
+    assert sum(n % 64 != 0 for n in Ns) >= 3
+    assert {1, 2, 5} <= {EDGE[f"{t}_code"].shape[0] for t in EDGE_GEO}
+    assert all(any(f"{t}_sim" not in EDGE.files for t in ts) for ts in (EDGE_APP, EDGE_GEO))
+    assert any((EDGE[f"{t}_depth"] > 15).reshape(EDGE[f"{t}_depth"].shape[0], -1).all(1).any()
+               or (EDGE[f"{t}_depth"] >= 15).reshape(EDGE[f"{t}_depth"].shape[0], -1).all(1).any() for t in EDGE_GEO)
+
+
+@pytest.mark.parametrize("tag", EDGE_APP)
+def test_correlation_loss_port_at_edge_shapes(tag):
+    S = EDGE[f"{tag}_rand1"].shape[1]
+    code = e(f"{tag}_code").clone().requires_grad_(True)
+    loss = lp.correlation_loss(e(f"{tag}_feats"), code, _edge_neg(tag), e(f"{tag}_rand1") * 2 - 1, e(f"{tag}_rand2") * 2 - 1,
+                               lp.CorrParams(*APP, feature_samples=S))
+    loss.backward()
+    want = EDGE[f"{tag}_loss"][0]
+    assert abs(loss.item() - want) <= 1e-6 * abs(want)
+    g = EDGE[f"{tag}_grad"]
+    assert np.abs(code.grad.numpy() - g).max() <= 1e-6 * np.abs(g).max()
+
+
+@pytest.mark.parametrize("tag", EDGE_GEO)
+def test_geo_correlation_loss_port_at_edge_shapes(tag):
+    depth = e(f"{tag}_depth").clone()
+    B, _, H, W = depth.shape
+    code = e(f"{tag}_code").clone().requires_grad_(True)
+    ray_o = e(f"{tag}_ray_o")[:, :, None, None].expand(B, 3, H, W)
+    loss = lp.geo_correlation_loss(depth, code, ray_o, e(f"{tag}_ray_d"), _edge_neg(tag), lp.CorrParams(*GEO))
+    loss.backward()
+    want = EDGE[f"{tag}_loss"][0]
+    assert abs(loss.item() - want) <= 1e-6 * abs(want)
+    assert np.array_equal(depth.numpy(), EDGE[f"{tag}_depth_after"])
+    d0 = EDGE[f"{tag}_depth"]                     # the filter: everything above 15 -> the batch-wide max below 15; 15 itself stays
+    assert np.array_equal(EDGE[f"{tag}_depth_after"][d0 > 15], np.full(int((d0 > 15).sum()), d0[d0 < 15].max(), np.float32))
+    assert (EDGE[f"{tag}_depth_after"][d0 == 15] == 15).all() and (d0 == 15).any()
+    g = EDGE[f"{tag}_grad"]
+    assert np.abs(code.grad.numpy() - g).max() <= 1e-6 * np.abs(g).max()
+
+
 CON = np.load(os.path.join(os.path.dirname(__file__), "golden", "contrastive.npz"))
 CON_CASES = sorted(k[:-4] for k in CON.files if k.endswith("_emb"))
 

@@ -30,8 +30,9 @@ extern "C" {
  * nsos_mlp_forward_rays_save16_lp and nsos_sem_head_wgrad_x3; 3: pose_rows in nsos_patch_batch / nsos_pixel_batch; 4: the tile-major
  * sem_hid16 of the default 16-bit kernel, nsos_mlp_save16_layout's NSOS_SEM_HID_TILED bit; 6: `scale` of nsos_mlp_input_grads_x3[_a16]
  * is three floats -- trunk scale, colour-branch factor, semantic-branch factor; 7: the generic kernels' packed program gained a field
- * (GenOp::ksplit_off: an older binding's buffer sizes still agree, but the two sides must match) + nsos_wgrad_batch) */
-#define NSOS_ABI_VERSION 8
+ * (GenOp::ksplit_off: an older binding's buffer sizes still agree, but the two sides must match) + nsos_wgrad_batch; 9: evaluation metrics
+ * nsos_ssim, nsos_adjusted_rand, nsos_kmeans) */
+#define NSOS_ABI_VERSION 9
 
 enum {
     NSOS_OK = 0,
@@ -558,6 +559,63 @@ size_t nsos_eval_workspace_bytes(void);
 int32_t nsos_eval_postprocess(const float* semantics, const float* rgb, const float* target, int64_t n_rays,
                               int32_t sem_dim, float* sem_prob, int32_t* sem_pred, float* metrics, void* workspace,
                               void* stream);
+
+/* ---- evaluation metrics: SSIM, k-means clustering, adjusted Rand index ---------------------------------------------
+ * The rest of engines/eval.py:31-93 (eval_one_view) and of the trainer's i_print block (engines/trainer.py:172-195) on the device.
+ * Every reduction runs in a fixed order (no float atomics): results are bitwise identical from run to run.
+ *
+ * nsos_ssim: utils/ssim.py:17-38 (_ssim) as reached through utils/image.py:139-147.  img1, img2 [batch, channels, height, width]
+ * (NCHW, dense).  window_size odd, 1..31: the gaussian of sigma 1.5 normalised in fp32 (utils/ssim.py:7-9), applied separably
+ * (its outer product) with zero padding window_size/2 per channel; C1 = 0.01^2, C2 = 0.03^2; moments and map in fp64.
+ * window: HOST pointer to the window_size fp32 weights of that 1-D window (the reference's torch expression, whose fp32 sum order is
+ * torch's), or NULL: the same gaussian normalised by its fp64-accumulated sum rounded to fp32.
+ * out: size_average != 0 -> out[0] = mean over batch*channels*height*width; else out[batch] = per-image means.  ssim_map
+ * [batch,channels,height,width] may be NULL.  workspace: nsos_ssim_workspace_bytes(...) bytes, 8-byte aligned. */
+size_t nsos_ssim_workspace_bytes(int64_t batch, int64_t channels, int64_t height, int64_t width);
+int32_t nsos_ssim(const float* img1, const float* img2, int64_t batch, int64_t channels, int64_t height, int64_t width,
+                  int32_t window_size, const float* window, int32_t size_average, float* out, float* ssim_map, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
+/* nsos_adjusted_rand: sklearn.metrics.adjusted_rand_score (1.x, pair-confusion form) of labels_true vs labels_pred [n], both of
+ * element type `dtype` (NSOS_LABEL_*; bool travels as UINT8).  Labels must be integers in [0, 64).  out (double [2]):
+ * out[0] = ARI over all n, out[1] = ARI over the positions where labels_true == subset_label (engines/eval.py:67-69 `fg_idx`),
+ * both from one contingency table.  Pair counts are exact (int64 sums, 128-bit products) and divided once in fp64; no
+ * disagreeing pairs (n <= 1, empty subset, one class on both sides) gives exactly 1.0.  Any label outside [0, 64) or not an
+ * integer makes both results NaN; their count is left in workspace word 4096 (uint64).  workspace:
+ * nsos_adjusted_rand_workspace_bytes() bytes, 8-byte aligned (the uint64 contingency table [64][64] + that count).  n <= 2^31. */
+enum { NSOS_LABEL_INT32 = 0, NSOS_LABEL_INT64 = 1, NSOS_LABEL_UINT8 = 2, NSOS_LABEL_FLOAT32 = 3 };
+size_t nsos_adjusted_rand_workspace_bytes(void);
+int32_t nsos_adjusted_rand(const void* labels_true, const void* labels_pred, int64_t n, int32_t dtype, int32_t subset_label,
+                           double* out, void* workspace, void* stream);
+
+/* nsos_kmeans: sklearn 1.x KMeans(algorithm="lloyd", n_init=1) on `batch` independent problems x [batch, n_points, n_features]
+ * (utils/misc.py:40-52 segmap_cluster).  n_features <= 16, n_clusters <= 16, n_points >= n_clusters.
+ *   - init_centers [batch, n_clusters, n_features] or NULL: greedy k-means++ (sklearn _kmeans_plusplus) with n_local_trials
+ *     candidates per round (0: 2 + floor(ln n_clusters)); each draw is the exponential race argmin_i -ln(u_i) / w_i (w = 1 for the
+ *     first center, D^2 after; ties to the lowest index) over the counter-based stream
+ *     s = mix(mix(mix(seed) ^ problem) ^ (round << 8 | trial)), u_i = ((mix(s ^ i) >> 40) + 1) / 2^24, mix = splitmix64's finaliser,
+ *     problem = problem_base + b / problems_per_stream (1: a stream per problem; batch: one stream shared by all, as per-slice
+ *     calls with one random_state draw).  The candidate of lowest potential (first on ties) is kept.
+ *   - Lloyd steps: nearest center (ties to the lowest index), fp64 per-cluster sums; an empty cluster takes the point farthest from
+ *     its assigned center (largest first, ties to the lowest index).  Stops when no label changed (strict convergence), when the
+ *     squared center shift <= tol * mean(var(x, axis=0)), or after max_iter steps; without strict convergence one more assignment
+ *     makes the labels agree with the returned centers.  max_iter = 0: seeding only (sklearn.cluster.kmeans_plusplus): the
+ *     centers are the seeds in draw order, labels the nearest seed, n_iter 0.
+ *   - labels int32 [batch, n_points] in canonical order: cluster r is the r-th center in ascending lexicographic order.  centers
+ *     [batch, n_clusters, n_features], inertia double [batch], n_iter int32 [batch] may each be NULL.
+ * mode 0: automatic (workgroup regime for n_points <= NSOS_KMEANS_WG_MAX_POINTS), 1: workgroup, 2: grid.
+ *   workgroup regime: one launch; one workgroup per problem runs seeding and every step.  Never synchronises.
+ *   grid regime: one seeding launch, then per step an assignment pass over all 1024-point chunks and a one-workgroup finish that
+ *   sets the problem's done word (later launches return at once); the host reads an all-done word after every 8 steps, so this
+ *   call synchronises `stream` ceil(n_iter / 8) times (at most ceil(max_iter / 8) - 1 times).  Both regimes run the same arithmetic
+ *   in the same order: bitwise-equal results.
+ * workspace: nsos_kmeans_workspace_bytes(...) bytes, 16-byte aligned. */
+#define NSOS_KMEANS_WG_MAX_POINTS 65536
+size_t nsos_kmeans_workspace_bytes(int64_t batch, int64_t n_points, int32_t n_features, int32_t n_clusters);
+int32_t nsos_kmeans(const float* x, int64_t batch, int64_t n_points, int32_t n_features, int32_t n_clusters, const float* init_centers,
+                    uint64_t seed, int64_t problem_base, int64_t problems_per_stream, int32_t n_local_trials, int32_t max_iter, double tol, int32_t mode,
+                    int32_t* labels, float* centers, double* inertia, int32_t* n_iter, void* workspace, size_t workspace_bytes,
+                    void* stream);
 
 /* Row-partitioned GeoCorrelationLoss for the ray/patch-sharded multi-GPU step (utils/image.py:448-487; call site
  * engines/trainer.py:159-160): every rank holds the WHOLE batch's depth / code / rays (sharding.all_gather_patches) but

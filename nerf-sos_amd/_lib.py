@@ -123,6 +123,13 @@ SIGNATURES = {
     "nsos_composite_backward": (_i32, [_fp, _fp, _fp, _fp, _f32, _i64, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "nsos_eval_workspace_bytes": (C.c_size_t, []),
     "nsos_eval_postprocess": (_i32, [_fp, _fp, _fp, _i64, _i32, _fp, _fp, _fp, _fp, _fp]),
+    "nsos_ssim_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "nsos_ssim": (_i32, [_fp, _fp, _i64, _i64, _i64, _i64, _i32, C.POINTER(C.c_float), _i32, _fp, _fp, _fp, _sz, _fp]),
+    "nsos_adjusted_rand_workspace_bytes": (_sz, []),
+    "nsos_adjusted_rand": (_i32, [_fp, _fp, _i64, _i32, _i32, _fp, _fp, _fp]),
+    "nsos_kmeans_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "nsos_kmeans": (_i32, [_fp, _i64, _i64, _i32, _i32, _fp, C.c_uint64, _i64, _i64, _i32, _i32, C.c_double, _i32, _fp, _fp, _fp, _fp,
+                           _fp, _sz, _fp]),
     "nsos_corr_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "nsos_app_correlation_loss": (_i32, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                          _f32, _f32, _f32, _f32, _fp, _fp, _fp, _sz, _fp]),
@@ -143,7 +150,7 @@ SIGNATURES = {
     "nsos_importance_sample": (_i32, [_fp, _fp, _fp, _fp, _i64, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp]),
 }
 
-ABI_VERSION = 8          # = NSOS_ABI_VERSION of include/nerf_sos_hip.h (an older .so is refused at load)
+ABI_VERSION = 9          # = NSOS_ABI_VERSION of include/nerf_sos_hip.h (an older .so is refused at load)
 _lib = None
 
 

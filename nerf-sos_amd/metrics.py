@@ -1,0 +1,98 @@
+"""Evaluation metrics with the reference's call shapes, all on the device: SSIM (utils/image.py:139-147), sklearn's
+adjusted_rand_score, segmap_cluster (utils/misc.py:40-52) and the metric blocks of engines/eval.py:31-93 (eval_one_view) and
+engines/trainer.py:172-195 (the i_print logging) -- everything those compute except LPIPS.
+
+The clustering is sklearn's KMeans(algorithm='lloyd') with greedy k-means++ seeding, but from this package's own counter-based
+random stream (nsos_kmeans): sklearn's stream cannot be reproduced, so a seeded clustering is a different, equally valid local
+optimum, and clus_ari moves inside the reference's own seed-to-seed spread.  With pinned initial centers the Lloyd loop follows
+sklearn's step by step.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+
+from . import ops
+
+
+def ssim(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11, size_average: bool = True,
+         format: str = "NCHW") -> torch.Tensor:
+    """utils/image.py:139-147: format 'HWC' [H,W,C], 'NHWC' or 'NCHW'.  A 1-element fp32 tensor, or [N] without size_average."""
+    if format == "HWC":
+        img1, img2 = img1.permute(2, 0, 1)[None], img2.permute(2, 0, 1)[None]
+    elif format == "NHWC":
+        img1, img2 = img1.permute(0, 3, 1, 2), img2.permute(0, 3, 1, 2)
+    elif format != "NCHW":
+        raise ValueError(f"ssim: unknown format {format!r}")
+    return ops.ssim(img1.contiguous(), img2.contiguous(), window_size, size_average)
+
+
+def adjusted_rand_score(labels_true: torch.Tensor, labels_pred: torch.Tensor) -> torch.Tensor:
+    """sklearn.metrics.adjusted_rand_score on device labelings: a 0-dim float64 tensor."""
+    return ops.adjusted_rand_score(labels_true, labels_pred)[0]
+
+
+def segmap_cluster(x: torch.Tensor, n_clusters: int = 2, seed: int = 0) -> torch.Tensor:
+    """utils/misc.py:40-52: k-means of the [H,W,C] map's pixels -> int32 labels [H,W,1].  A leading batch dimension [B,H,W,C]
+    clusters every slice on its own, in one launch ([B,H,W,1]); every slice draws from the same seed stream, so the batch equals
+    per-slice calls (the trainer's loop, each with random_state=0)."""
+    if x.dim() not in (3, 4):
+        raise ValueError(f"segmap_cluster: x must be [H,W,C] or [B,H,W,C], got {tuple(x.shape)}")
+    lead = tuple(x.shape[:-1])
+    xb = x.float().reshape(1 if x.dim() == 3 else x.shape[0], -1, x.shape[-1])
+    return ops.kmeans(xb, n_clusters, seed=seed, shared_stream=True)["labels"].reshape(*lead, 1)
+
+
+def _labels_of(masks: torch.Tensor) -> torch.Tensor:
+    if masks.dtype in ops.LABEL_DTYPES:
+        return masks
+    return masks.float()
+
+
+def view_metrics(ret: Dict[str, torch.Tensor], target_s: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None,
+                 N_cluster: int = 2, clus_no_sfm: bool = False, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """eval_one_view's metric_dict (mse psnr ssim clus_ari clus_ari_fg sem_ari sem_ari_fg; no lpips) plus `sem` (argmax of the
+    softmax, int32 [...,1]) and `clustering` (int32 [...,1]) on the device, from the render `ret` ('rgb' [H,W,3] and 'semantics'
+    [H,W,C]; a ray list [R,3] / [R,C] works as well, except for SSIM, which needs the image).  masks: the ground-truth labels
+    (engines/eval.py:45 `batch['masks']`), fg = masks == 1.  The ARIs and SSIM are fp32 1-element tensors, as the reference's."""
+    out: Dict[str, torch.Tensor] = {}
+    sem = ret.get("semantics")
+    rgb = ret.get("rgb")
+    have_rgb = rgb is not None and target_s is not None
+    pp = ops.eval_postprocess(sem, rgb if have_rgb else None, target_s if have_rgb else None)
+    if have_rgb:
+        out["mse"], out["psnr"] = pp["mse"], pp["psnr"]
+        if rgb.dim() == 3:
+            out["ssim"] = ssim(rgb, target_s.to(rgb.device), format="HWC")
+    if sem is not None:
+        dev = sem.device
+        feats = sem.float() if clus_no_sfm else pp["sem_prob"]   # engines/eval.py:49-54
+        clus = ops.kmeans(feats.reshape(-1, feats.shape[-1]), N_cluster, seed=seed)["labels"]   # segmap_cluster, any layout
+        out["sem"] = pp["sem"]
+        out["clustering"] = clus.reshape(*feats.shape[:-1], 1)
+        if masks is not None:
+            gt = _labels_of(masks.to(dev)).reshape(-1)
+            c = ops.adjusted_rand_score(gt, out["clustering"].reshape(-1).to(gt.dtype))
+            s = ops.adjusted_rand_score(gt, out["sem"].reshape(-1).to(gt.dtype))
+            vals = torch.cat([c, s]).float()
+        else:
+            vals = torch.zeros(4, device=dev, dtype=torch.float32)
+        out["clus_ari"], out["clus_ari_fg"], out["sem_ari"], out["sem_ari_fg"] = vals[0:1], vals[1:2], vals[2:3], vals[3:4]
+    return out
+
+
+def patch_metrics(semantics: torch.Tensor, masks: torch.Tensor, N_cluster: int = 2, clus_no_sfm: bool = False,
+                  seed: int = 0) -> Dict[str, torch.Tensor]:
+    """engines/trainer.py:173-192 on the device: semantics [B,P,P,C], masks [B,P,P] or [B,P,P,1].  Every patch is clustered on
+    its own (one launch for the batch); the four ARIs pool all patches.  Returns clus_ari, clus_ari_fg, sem_ari, sem_ari_fg as
+    0-dim float64 tensors plus `sem` and `clustering` (int32 [B,P,P,1])."""
+    if semantics.dim() != 4:
+        raise ValueError(f"patch_metrics: semantics must be [B,P,P,C], got {tuple(semantics.shape)}")
+    pp = ops.eval_postprocess(semantics)
+    feats = semantics.float() if clus_no_sfm else pp["sem_prob"]
+    clus = segmap_cluster(feats, N_cluster, seed)
+    gt = _labels_of(masks.to(semantics.device)).reshape(-1)
+    c = ops.adjusted_rand_score(gt, clus.reshape(-1).to(gt.dtype))
+    s = ops.adjusted_rand_score(gt, pp["sem"].reshape(-1).to(gt.dtype))
+    return {"clus_ari": c[0], "clus_ari_fg": c[1], "sem_ari": s[0], "sem_ari_fg": s[1], "sem": pp["sem"], "clustering": clus}

@@ -908,6 +908,113 @@ def eval_postprocess(semantics: Optional[torch.Tensor] = None, rgb: Optional[tor
     return out
 
 
+# ------------------------------------------------------------------------------------------ evaluation metrics
+@functools.lru_cache(maxsize=None)
+def ssim_window(window_size: int, sigma: float = 1.5):
+    """utils/ssim.py:7-9 `gaussian` as the reference evaluates it (a host fp32 tensor divided by torch's fp32 sum), as a ctypes
+    array for nsos_ssim (a host-side constant of 1 to 31 floats)."""
+    import math
+    if window_size < 1 or window_size > 31 or window_size % 2 == 0:
+        return None                                    # the C ABI rejects it
+    g = torch.Tensor([math.exp(-(x - window_size // 2) ** 2 / float(2 * sigma ** 2)) for x in range(window_size)])
+    g = g / g.sum()
+    return (C.c_float * window_size)(*g.tolist())
+
+
+def ssim(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11, size_average: bool = True,
+         return_map: bool = False):
+    """utils/ssim.py:66-73 on NCHW fp32 images [N,C,H,W]: a 1-element tensor (size_average) or the per-image means [N], and
+    with return_map also the per-pixel map [N,C,H,W].  Deterministic (fixed-order fp64 reductions)."""
+    img1, img2 = _dev(img1, "img1"), _dev(img2, "img2")
+    if img1.dim() != 4 or tuple(img1.shape) != tuple(img2.shape):
+        raise ValueError(f"ssim needs two NCHW images of one shape, got {tuple(img1.shape)} and {tuple(img2.shape)}")
+    N, Ch, H, W = (int(v) for v in img1.shape)
+    dev = img1.device
+    out = torch.empty((1 if size_average else N,), device=dev, dtype=torch.float32)
+    smap = torch.empty_like(img1) if return_map else None
+    nbytes = int(_lib.lib().nsos_ssim_workspace_bytes(N, Ch, H, W))
+    ws = torch.empty((max(nbytes, 8) // 8,), device=dev, dtype=torch.float64)
+    win = ssim_window(int(window_size))
+    _lib.check(_lib.lib().nsos_ssim(_p(img1), _p(img2), N, Ch, H, W, int(window_size), win, int(bool(size_average)), _p(out),
+                                    _p(smap), _p(ws), nbytes, _stream()), "nsos_ssim")
+    return (out, smap) if return_map else out
+
+
+LABEL_DTYPES = {torch.int32: 0, torch.int64: 1, torch.uint8: 2, torch.bool: 2, torch.float32: 3}   # NSOS_LABEL_*
+
+
+def adjusted_rand_score(labels_true: torch.Tensor, labels_pred: torch.Tensor, subset_label: int = 1) -> torch.Tensor:
+    """sklearn adjusted_rand_score of two device labelings of one element type (int32 / int64 / uint8 / bool / float32; labels
+    must be integers in [0, 64), anything else gives NaN).  Returns float64 [2]: the ARI over all elements and the ARI over the
+    elements where labels_true == subset_label (the reference's `*_fg`), from one contingency table."""
+    if not isinstance(labels_true, torch.Tensor) or not labels_true.is_cuda or not isinstance(labels_pred, torch.Tensor) or not labels_pred.is_cuda:
+        raise RuntimeError("nerf_sos_amd: adjusted_rand_score needs GPU tensors -- this package has no CPU path")
+    if labels_pred.dtype != labels_true.dtype:
+        labels_pred = labels_pred.to(labels_true.dtype)
+    if labels_true.dtype not in LABEL_DTYPES:
+        raise TypeError(f"adjusted_rand_score: unsupported label type {labels_true.dtype}")
+    lt, lp = labels_true.reshape(-1).contiguous(), labels_pred.reshape(-1).contiguous()
+    if lt.numel() != lp.numel():
+        raise ValueError(f"adjusted_rand_score: {lt.numel()} true labels vs {lp.numel()} predicted")
+    dev = lt.device
+    out = torch.empty((2,), device=dev, dtype=torch.float64)
+    ws = torch.empty((int(_lib.lib().nsos_adjusted_rand_workspace_bytes()) // 8,), device=dev, dtype=torch.int64)
+    _lib.check(_lib.lib().nsos_adjusted_rand(_p(lt), _p(lp), lt.numel(), LABEL_DTYPES[lt.dtype], int(subset_label), _p(out), _p(ws),
+                                             _stream()), "nsos_adjusted_rand")
+    return out
+
+
+KMEANS_MODES = {"auto": 0, "workgroup": 1, "grid": 2}
+
+
+def kmeans(x: torch.Tensor, n_clusters: int, init: Optional[torch.Tensor] = None, seed: int = 0, n_init: int = 1,
+           max_iter: int = 300, tol: float = 1e-4, n_local_trials: int = 0, problem_offset: int = 0,
+           shared_stream: bool = False, mode: str = "auto") -> Dict[str, torch.Tensor]:
+    """sklearn KMeans(n_clusters, algorithm='lloyd') on x [B,N,C] (or [N,C]): B independent problems in one call.
+    Returns labels int32 [B,N] (canonical order: ascending lexicographic order of the centers), centers [B,K,C], inertia float64
+    [B] and n_iter int32 [B] (without the B dimension for a 2-D x).  init [B,K,C] pins the initial centers; otherwise greedy
+    k-means++ seeded from (seed, problem_offset + b) -- see nsos_kmeans; shared_stream=True seeds every problem from
+    (seed, problem_offset), as separate calls with one random_state would.  n_init > 1 runs the extra seeds as extra problems
+    (problem ids problem_offset + i * B + b, or problem_offset + i when shared) in the same launch and keeps the lowest inertia
+    (first on ties).
+    max_iter=0 returns the k-means++ seeds themselves, in draw order (sklearn.cluster.kmeans_plusplus).
+    mode "auto" / "workgroup" / "grid" (see nsos_kmeans: the grid regime synchronises the stream every 8 Lloyd steps)."""
+    x = _dev(x, "x")
+    squeeze = x.dim() == 2
+    if squeeze:
+        x = x[None]
+    if x.dim() != 3:
+        raise ValueError(f"kmeans: x must be [B,N,C] or [N,C], got {tuple(x.shape)}")
+    B, N, Cf = (int(v) for v in x.shape)
+    K = int(n_clusters)
+    if init is not None:
+        init = _dev(init, "init").reshape(B, K, Cf)
+        n_init = 1
+    if n_init < 1:
+        raise ValueError("kmeans: n_init must be >= 1")
+    P = B * n_init
+    xs = x if n_init == 1 else x.repeat(n_init, 1, 1).contiguous()
+    dev = x.device
+    labels = torch.empty((P, N), device=dev, dtype=torch.int32)
+    centers = torch.empty((P, K, Cf), device=dev, dtype=torch.float32)
+    inertia = torch.empty((P,), device=dev, dtype=torch.float64)
+    n_iter = torch.empty((P,), device=dev, dtype=torch.int32)
+    nbytes = int(_lib.lib().nsos_kmeans_workspace_bytes(P, N, Cf, K))
+    ws = torch.empty((max(nbytes, 16) // 8 + 2,), device=dev, dtype=torch.float64)
+    _lib.check(_lib.lib().nsos_kmeans(_p(xs), P, N, Cf, K, _p(init), int(seed) & 0xFFFFFFFFFFFFFFFF, int(problem_offset),
+                                      B if shared_stream else 1,
+                                      int(n_local_trials), int(max_iter), float(tol), KMEANS_MODES[mode], _p(labels), _p(centers),
+                                      _p(inertia), _p(n_iter), _p(ws), ws.numel() * 8, _stream()), "nsos_kmeans")
+    if n_init > 1:
+        best = inertia.view(n_init, B).argmin(0)          # first minimal: the lowest init on ties
+        rows = best * B + torch.arange(B, device=dev)
+        labels, centers, inertia, n_iter = labels[rows], centers[rows], inertia[rows], n_iter[rows]
+    out = {"labels": labels, "centers": centers, "inertia": inertia, "n_iter": n_iter}
+    if squeeze:
+        out = {k: v[0] for k, v in out.items()}
+    return out
+
+
 # ------------------------------------------------------------------------------------------ K7: full backward
 ACTS_FEAT, ACTS_VIEWS, ACTS_SEM, ACTS_X, ACTS_D, ACTS_DIM = 2048, 2304, 2432, 2560, 2624, 2656   # nerf_sos_hip.h
 

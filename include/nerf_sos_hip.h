@@ -31,8 +31,8 @@ extern "C" {
  * sem_hid16 of the default 16-bit kernel, nsos_mlp_save16_layout's NSOS_SEM_HID_TILED bit; 6: `scale` of nsos_mlp_input_grads_x3[_a16]
  * is three floats -- trunk scale, colour-branch factor, semantic-branch factor; 7: the generic kernels' packed program gained a field
  * (GenOp::ksplit_off: an older binding's buffer sizes still agree, but the two sides must match) + nsos_wgrad_batch; 9: evaluation metrics
- * nsos_ssim, nsos_adjusted_rand, nsos_kmeans) */
-#define NSOS_ABI_VERSION 9
+ * nsos_ssim, nsos_adjusted_rand, nsos_kmeans; 10: the DINO ViT-S/16 feature extractor nsos_dino_*) */
+#define NSOS_ABI_VERSION 10
 
 enum {
     NSOS_OK = 0,
@@ -719,6 +719,74 @@ int32_t nsos_geo_correlation_loss(float* depth, const float* code, const float* 
                                   int32_t width, float self_shift, float self_weight, float neg_shift,
                                   float neg_weight, float max_depth, int32_t filter_in_place, float* loss,
                                   float* grad_code, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- DINO ViT-S/16 feature extractor (forward only, fp32) ----------------------------------------------------------
+ * What engines/trainer.py:101-109 runs between the render and the losses: the rendered patches through a frozen DINO
+ * ViT-S/16 (models/extractor.py:204-213 get_vit_attn_feat over models/vision_transformer.py vit_small(patch_size=16)).
+ *   1. engines/trainer.py:103-106: channels first, F.interpolate(x, (h*stride, w*stride)) (nearest), (x - mean) / std;
+ *   2. models/extractor.py:207-208: F.interpolate(x, size=(224,224)) (nearest), (x - mean) / std (again: kept);
+ *      both resizes use torch's index rule min(floor(dst * (float)in / out), in - 1) with the product in fp32 and compose into one
+ *      gather; subtract and divide are rounded separately (the prepared image is bit-equal to torch's);
+ *   3. models/vision_transformer.py:196-215: 16x16 patch embedding, class token, + pos_embed, 12 blocks
+ *      x += proj(attn(LN(x))); x += fc2(GELU(fc1(LN(x)))); LayerNorm eps 1e-6, 6 heads of 64, scale 1/8, erf GELU;
+ *   4. models/extractor.py:109-117,209-212: block 11's output BEFORE the final norm: cls = x[:,0], feat = x[:,1:];
+ *      attn = block 11's softmax, mean over the heads (h = 0..5 summed in that order, then / 6), row 0, columns 1..196.
+ * Depth / width / heads are compile-time constants; the batch is a runtime argument (1..NSOS_DINO_MAX_BATCH).
+ * Accumulation order (fixed: two runs give the same bits, and an image's result does not depend on the batch around it):
+ * every GEMM output element is ONE fp32 fma chain over k = 0..K-1 ascending starting from 0 (v_mfma_f32_32x32x2_f32), then
+ * + bias, then GELU, then + residual; q.k sums d = 0..63 ascending, softmax.v sums the keys 0..196 ascending (v_mfma_f32_16x16x4_f32);
+ * LayerNorm / softmax row sums: six (four) strided elements per lane ascending, then an xor butterfly 32,16,8,4,2,1 over the wave. */
+#define NSOS_DINO_DEPTH 12
+#define NSOS_DINO_WIDTH 384
+#define NSOS_DINO_HEADS 6
+#define NSOS_DINO_TOKENS 197 /* 1 + 14*14 */
+#define NSOS_DINO_IMAGE 224
+#define NSOS_DINO_PATCH 16
+#define NSOS_DINO_HIDDEN 1536
+#define NSOS_DINO_MAX_BATCH 1024
+
+/* DINO's checkpoint tensors (device fp32, nn.Linear / nn.Conv2d layout as in the state dict).  norm.weight / norm.bias are not
+ * here: the final norm is never applied on this path. */
+typedef struct nsos_dino_block_tensors {
+    const float *norm1_w, *norm1_b; /* blocks.i.norm1.*       [384] */
+    const float *qkv_w, *qkv_b;     /* blocks.i.attn.qkv.*    [1152,384] [1152] */
+    const float *proj_w, *proj_b;   /* blocks.i.attn.proj.*   [384,384] [384] */
+    const float *norm2_w, *norm2_b; /* blocks.i.norm2.*       [384] */
+    const float *fc1_w, *fc1_b;     /* blocks.i.mlp.fc1.*     [1536,384] [1536] */
+    const float *fc2_w, *fc2_b;     /* blocks.i.mlp.fc2.*     [384,1536] [384] */
+} nsos_dino_block_tensors;
+typedef struct nsos_dino_tensors {
+    const float* cls_token;         /* [1,1,384] */
+    const float* pos_embed;         /* [1,197,384] */
+    const float *patch_w, *patch_b; /* patch_embed.proj.*     [384,3,16,16] [384] */
+    nsos_dino_block_tensors blocks[NSOS_DINO_DEPTH];
+} nsos_dino_tensors;
+
+/* The frozen network is packed once into the stream the kernels read: every weight matrix transposed to [in,out] (the GEMM's
+ * B operand, streamed row by row), biases and LayerNorm vectors as they are, pos_embed with row 0 replaced by cls_token + pos_embed[0].
+ * `packed`: nsos_dino_packed_bytes() bytes, 16-byte aligned.  Call again whenever a parameter changes. */
+size_t nsos_dino_packed_bytes(void);
+int32_t nsos_dino_pack(const nsos_dino_tensors* tensors, void* packed, size_t packed_bytes, void* stream);
+
+/* flags of nsos_dino_forward */
+enum {
+    NSOS_DINO_NHWC = 1,     /* input is [B,h,w,3] (the renderer's rgb) instead of [B,3,h,w] */
+    NSOS_DINO_STEP1 = 2,    /* also do the trainer's step 1 (resize to (h*stride, w*stride) and normalise) before step 2 */
+    NSOS_DINO_PREPARED = 4  /* input is an already prepared [B,3,224,224] image: steps 1-2 skipped (excludes the other two) */
+};
+/* workspace: nsos_dino_workspace_bytes(batch) bytes (0 for a batch outside 1..NSOS_DINO_MAX_BATCH), 16-byte aligned, contents
+ * undefined on return.  Outputs, each optional (NULL to skip): feat [B,196,384], cls [B,384], attn [B,1,196],
+ * prepared [B,3,224,224] (the image after steps 1-2), blocks [12,B,197,384] (every block's output: localises a difference).
+ * Everything is validated before anything is launched or written.  No host synchronisation, no allocation: capturable.  The one-time
+ * per-device kernel attribute (the attention kernel's dynamic LDS size) is set by nsos_dino_pack as well, so a forward call whose first
+ * use is inside a stream capture has nothing left to configure; if setting it fails the positive hipError_t is returned. */
+size_t nsos_dino_workspace_bytes(int32_t batch);
+int32_t nsos_dino_forward(const float* input, int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags,
+                          const void* packed, void* workspace, size_t workspace_bytes, float* feat, float* cls, float* attn,
+                          float* prepared, float* blocks, void* stream);
+/* Host helper: the source index of each of the 224 output rows (or columns) of steps 1-2 for an input extent `in_size`
+ * (patch_stride <= 0: step 2 alone), exactly the rule the prepare kernel evaluates.  idx: HOST int32 [224]. */
+int32_t nsos_dino_resize_indices(int32_t in_size, int32_t patch_stride, int32_t* idx);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,8 @@ from . import synthetic  # noqa: F401
 from . import quality  # noqa: F401
 from . import metrics  # noqa: F401
 from .graphs import GraphedPatchStep, GraphedRender  # noqa: F401
+from . import dino  # noqa: F401
+from .dino import DinoViT  # noqa: F401
 from .losses import CorrelationLoss, GeoCorrelationLoss, NeRFContrastive  # noqa: F401
 
-__all__ = ["NeRFNet", "NeRFMLP", "MLP", "export_density", "ops", "sharding", "losses", "io", "synthetic", "quality", "metrics", "CorrelationLoss", "GeoCorrelationLoss", "NeRFContrastive", "GraphedRender", "GraphedPatchStep"]
+__all__ = ["NeRFNet", "NeRFMLP", "MLP", "export_density", "ops", "sharding", "losses", "io", "synthetic", "quality", "metrics", "CorrelationLoss", "GeoCorrelationLoss", "NeRFContrastive", "GraphedRender", "GraphedPatchStep", "dino", "DinoViT"]

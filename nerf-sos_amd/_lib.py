@@ -42,6 +42,20 @@ class WgradItem(C.Structure):
     _fields_ = [("w_off", _i64), ("b_off", _i64), ("g_col", _i32), ("x_col", _i32), ("M", _i32), ("N", _i32), ("ldw", _i32), ("reserved", _i32)]
 
 
+class DinoBlockTensors(C.Structure):
+    """struct nsos_dino_block_tensors"""
+    _fields_ = [(n, _fp) for n in ("norm1_w", "norm1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "norm2_w", "norm2_b",
+                                   "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+
+
+DINO_DEPTH = 12
+
+
+class DinoTensors(C.Structure):
+    """struct nsos_dino_tensors"""
+    _fields_ = [("cls_token", _fp), ("pos_embed", _fp), ("patch_w", _fp), ("patch_b", _fp), ("blocks", DinoBlockTensors * DINO_DEPTH)]
+
+
 # name -> (restype, argtypes); must list every symbol the header declares (tests/test_abi.py checks)
 SIGNATURES = {
     "nsos_abi_version": (_i32, []),
@@ -130,6 +144,11 @@ SIGNATURES = {
     "nsos_kmeans_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "nsos_kmeans": (_i32, [_fp, _i64, _i64, _i32, _i32, _fp, C.c_uint64, _i64, _i64, _i32, _i32, C.c_double, _i32, _fp, _fp, _fp, _fp,
                            _fp, _sz, _fp]),
+    "nsos_dino_packed_bytes": (_sz, []),
+    "nsos_dino_pack": (_i32, [C.POINTER(DinoTensors), _fp, _sz, _fp]),
+    "nsos_dino_workspace_bytes": (_sz, [_i32]),
+    "nsos_dino_forward": (_i32, [_fp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "nsos_dino_resize_indices": (_i32, [_i32, _i32, C.POINTER(C.c_int32)]),
     "nsos_corr_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "nsos_app_correlation_loss": (_i32, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                          _f32, _f32, _f32, _f32, _fp, _fp, _fp, _sz, _fp]),
@@ -150,7 +169,7 @@ SIGNATURES = {
     "nsos_importance_sample": (_i32, [_fp, _fp, _fp, _fp, _i64, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp]),
 }
 
-ABI_VERSION = 9          # = NSOS_ABI_VERSION of include/nerf_sos_hip.h (an older .so is refused at load)
+ABI_VERSION = 10         # = NSOS_ABI_VERSION of include/nerf_sos_hip.h (an older .so is refused at load)
 _lib = None
 
 

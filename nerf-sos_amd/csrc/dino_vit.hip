@@ -1,0 +1,419 @@
+// DINO ViT-S/16 feature extractor, forward only, fp32 (include/nerf_sos_hip.h "DINO ViT-S/16").
+// Replaces engines/trainer.py:103-106 (resize + normalize_batch), models/extractor.py:204-213 (get_vit_attn_feat) and
+// models/vision_transformer.py:196-215 (vit_small(patch_size=16): prepare_tokens + 12 blocks) with four kernels:
+//   dino_prepare_kernel   steps 1-2 (two nearest resizes as one gather, two normalisations) fused with the patch embedding's im2col
+//   dino_gemm_kernel      C = A[M,K] . Wt[K,N] on v_mfma_f32_32x32x2_f32, epilogue bias / GELU / residual / (embedding) + pos_embed
+//   dino_layernorm_kernel one wave per token row of 384
+//   dino_attention_kernel one workgroup per (32 query rows, head, image) on v_mfma_f32_16x16x4_f32
+// Every sum runs in a fixed order (the header states it); no atomics; each workgroup reads one image only, so an image's bits do
+// not depend on the batch it travels in.
+#include "common.h"
+#include "mlp_common.h"
+
+namespace {
+
+constexpr int D = NSOS_DINO_WIDTH, T = NSOS_DINO_TOKENS, NP = T - 1, HEADS = NSOS_DINO_HEADS, HD = 64, HID = NSOS_DINO_HIDDEN;
+constexpr int IMG = NSOS_DINO_IMAGE, PS = NSOS_DINO_PATCH, GRID = IMG / PS, KE = 3 * PS * PS;   // 14 patches a side, 768 inputs each
+static_assert(D == HEADS * HD && NP == GRID * GRID, "ViT-S/16 geometry");
+
+// ---- packed stream (floats) ----------------------------------------------------------------------------------------------------
+constexpr size_t P_POS = 0;                                  // [197][384], row 0 = cls_token + pos_embed[0]
+constexpr size_t P_EMB_W = P_POS + (size_t)T * D;            // [768][384]  (patch_embed.proj.weight transposed)
+constexpr size_t P_EMB_B = P_EMB_W + (size_t)KE * D;
+constexpr size_t P_BLOCKS = P_EMB_B + D;
+constexpr size_t B_LN1W = 0, B_LN1B = B_LN1W + D, B_QKVW = B_LN1B + D, B_QKVB = B_QKVW + (size_t)D * 3 * D, B_PROJW = B_QKVB + 3 * D,
+                 B_PROJB = B_PROJW + (size_t)D * D, B_LN2W = B_PROJB + D, B_LN2B = B_LN2W + D, B_FC1W = B_LN2B + D,
+                 B_FC1B = B_FC1W + (size_t)D * HID, B_FC2W = B_FC1B + HID, B_FC2B = B_FC2W + (size_t)HID * D, B_SIZE = B_FC2B + D;
+constexpr size_t P_SIZE = P_BLOCKS + (size_t)NSOS_DINO_DEPTH * B_SIZE;
+static_assert(P_EMB_W % 4 == 0 && P_BLOCKS % 4 == 0 && B_SIZE % 4 == 0 && B_QKVW % 4 == 0 && B_FC2W % 4 == 0, "float4 rows");
+
+// ---- workspace (floats per image) ----------------------------------------------------------------------------------------------
+constexpr size_t W_X = 0, W_LN = W_X + (size_t)T * D, W_QKV = W_LN + (size_t)T * D, W_AO = W_QKV + (size_t)T * 3 * D,
+                 W_HID = W_AO + (size_t)T * D, W_TOK = W_HID + (size_t)T * HID, W_ROW0 = W_TOK + (size_t)NP * KE,
+                 W_SIZE = W_ROW0 + (size_t)HEADS * NP;
+static_assert(W_SIZE % 4 == 0 && W_LN % 4 == 0 && W_QKV % 4 == 0 && W_TOK % 4 == 0, "16-byte aligned sections for every batch size");
+
+// torch's `nearest` source index (ATen UpSample.h nearest_neighbor_compute_source_index): scale and product in fp32
+__host__ __device__ inline int dino_nearest(int dst, int in, int out) {
+    const float scale = (float)in / (float)out;
+    const int s = (int)floorf((float)dst * scale);
+    return s < in - 1 ? s : in - 1;
+}
+// steps 1-2 composed: 224 -> in*stride -> in  (stride <= 0: 224 -> in)
+__host__ __device__ inline int dino_source_index(int dst, int in, int stride) {
+    if (stride <= 0) return dino_nearest(dst, in, IMG);
+    const int mid = in * stride;
+    return dino_nearest(dino_nearest(dst, mid, IMG), in, mid);
+}
+
+// ---- prepare: tokens[b*196 + t][c*256 + py*16 + px] = prepared[b][c][16*ty + py][16*tx + px]; also x[b][0][:] = cls + pos[0] ----
+__global__ __launch_bounds__(256) void dino_prepare_kernel(const float* __restrict__ in, int batch, int in_h, int in_w, int stride, int flags,
+                                                           const float* __restrict__ clspos, float* __restrict__ tokens, float* __restrict__ x,
+                                                           float* __restrict__ prepared) {
+    const long long n = (long long)batch * NP * KE;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const int k = (int)(e % KE);
+    const int t = (int)((e / KE) % NP);
+    const int b = (int)(e / ((long long)KE * NP));
+    const int c = k >> 8, py = (k >> 4) & 15, px = k & 15;
+    const int y = (t / GRID) * PS + py, xx = (t % GRID) * PS + px;
+    float v;
+    if (flags & NSOS_DINO_PREPARED) {
+        v = in[(((size_t)b * 3 + c) * IMG + y) * IMG + xx];
+    } else {
+        const int s1 = (flags & NSOS_DINO_STEP1) ? stride : 0;
+        const int sy = dino_source_index(y, in_h, s1), sx = dino_source_index(xx, in_w, s1);
+        v = (flags & NSOS_DINO_NHWC) ? in[(((size_t)b * in_h + sy) * in_w + sx) * 3 + c] : in[(((size_t)b * 3 + c) * in_h + sy) * in_w + sx];
+        const float mean = c == 0 ? 0.485f : (c == 1 ? 0.456f : 0.406f), sd = c == 0 ? 0.229f : (c == 1 ? 0.224f : 0.225f);
+        if (flags & NSOS_DINO_STEP1) v = (v - mean) / sd;   // engines/trainer.py:24-29 normalize_batch
+        v = (v - mean) / sd;                                // models/extractor.py:205-208
+    }
+    tokens[e] = v;
+    if (prepared) prepared[(((size_t)b * 3 + c) * IMG + y) * IMG + xx] = v;
+    if (t == 0 && k < D) x[(size_t)b * T * D + k] = clspos[k];
+}
+
+// ---- GEMM: out[M,N] = epilogue(A[M,K] . Wt[K,N]).  64x64 outputs per workgroup, four waves of 32x32, K in steps of 32 through LDS.
+enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_EMBED = 3 };
+constexpr int GM = 64, GN = 64, GK = 32, LDA = GK + 1;   // odd A stride: the 32 rows a wave reads per k fall in 32 banks
+
+// K is a template parameter: a constant trip count, and proj (K 384) / fc2 (K 1536) show up as separate kernels in a trace.
+template <int EPI, int K>
+__global__ __launch_bounds__(256) void dino_gemm_kernel(const float* __restrict__ A, const float* __restrict__ Wt, const float* __restrict__ bias,
+                                                        float* out, const float* extra, int M, int N) {
+    __shared__ float As[GM * LDA];
+    __shared__ __attribute__((aligned(16))) float Bs[GK * GN];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int m0 = blockIdx.y * GM, n0 = blockIdx.x * GN;
+    const int ar = tid >> 3, ak = (tid & 7) * 4;    // A tile 64x32: two float4 per thread (rows ar, ar + 32)
+    const int bk = tid >> 4, bn = (tid & 15) * 4;   // B tile 32x64: two float4 per thread (rows bk, bk + 16)
+    const int row0 = min(m0 + ar, M - 1), row1 = min(m0 + ar + 32, M - 1);   // rows past M repeat the last one; never stored
+    float4 ra0, ra1, rb0, rb1;
+    auto gload = [&](int k0) {
+        ra0 = *reinterpret_cast<const float4*>(A + (size_t)row0 * K + k0 + ak);
+        ra1 = *reinterpret_cast<const float4*>(A + (size_t)row1 * K + k0 + ak);
+        rb0 = *reinterpret_cast<const float4*>(Wt + (size_t)(k0 + bk) * N + n0 + bn);
+        rb1 = *reinterpret_cast<const float4*>(Wt + (size_t)(k0 + bk + 16) * N + n0 + bn);
+    };
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
+    gload(0);
+    const int a_off = (wm * 32 + (lane & 31)) * LDA + (lane >> 5), b_off = (lane >> 5) * GN + wn * 32 + (lane & 31);
+    for (int k0 = 0; k0 < K; k0 += GK) {
+        __syncthreads();   // the previous tile has been consumed
+        float* a0 = As + ar * LDA + ak;
+        a0[0] = ra0.x, a0[1] = ra0.y, a0[2] = ra0.z, a0[3] = ra0.w;
+        float* a1 = a0 + 32 * LDA;
+        a1[0] = ra1.x, a1[1] = ra1.y, a1[2] = ra1.z, a1[3] = ra1.w;
+        *reinterpret_cast<float4*>(Bs + bk * GN + bn) = rb0;
+        *reinterpret_cast<float4*>(Bs + (bk + 16) * GN + bn) = rb1;
+        __syncthreads();
+        if (k0 + GK < K) gload(k0 + GK);   // in flight under this tile's MFMAs
+#pragma unroll
+        for (int kk = 0; kk < GK; kk += 2)   // k ascending: one fma chain per output element
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[a_off + kk], Bs[b_off + kk * GN], acc, 0, 0, 0);
+    }
+    const int col = n0 + wn * 32 + (lane & 31);
+    const float bv = bias[col];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (row >= M) continue;
+        float v = acc[r] + bv;
+        if constexpr (EPI == EPI_GELU) v = v * 0.5f * (1.0f + erff(v * 0.70710678118654752440f));
+        if constexpr (EPI == EPI_RESIDUAL) v = extra[(size_t)row * N + col] + v;
+        if constexpr (EPI == EPI_EMBED) {   // row = b*196 + t -> token row b*197 + 1 + t; + pos_embed[1 + t]
+            const int b = row / NP, t = row - b * NP;
+            v = v + extra[(size_t)(1 + t) * N + col];
+            out[((size_t)b * T + 1 + t) * N + col] = v;
+        } else {
+            out[(size_t)row * N + col] = v;
+        }
+    }
+}
+
+__device__ __forceinline__ float dino_wave_sum(float v) {   // xor butterfly 32,16,8,4,2,1: every lane ends with the same bits
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+__device__ __forceinline__ float dino_wave_max(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+    return v;
+}
+
+// ---- LayerNorm over 384, eps 1e-6 (biased variance about the mean, as nn.LayerNorm); one wave per row ---------------------------
+__global__ __launch_bounds__(256) void dino_layernorm_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+                                                             float* __restrict__ y, int M) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const float* xr = x + (size_t)row * D;
+    float v[6], s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[j] = xr[lane + 64 * j], s += v[j];
+    const float mean = dino_wave_sum(s) / (float)D;
+    float q = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[j] -= mean, q += v[j] * v[j];
+    const float rstd = 1.0f / sqrtf(dino_wave_sum(q) / (float)D + 1e-6f);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) y[(size_t)row * D + lane + 64 * j] = v[j] * rstd * w[lane + 64 * j] + b[lane + 64 * j];
+}
+
+// ---- attention (models/vision_transformer.py:80-92): softmax(q k^T / 8) v for 32 query rows of one head of one image -----------
+constexpr int QT = 32, LDQ = 66, LDK = 66, LDV = 80, TP = 200, LDP = 226;   // strides: conflict-free 16x16x4 operand reads (32 banks)
+constexpr int KV_FLOATS = (T * LDK > TP * LDV) ? T * LDK : TP * LDV;
+constexpr int ATT_LDS_BYTES = (QT * LDQ + KV_FLOATS + QT * LDP) * 4;
+static_assert(ATT_LDS_BYTES <= 160 * 1024, "one CU's LDS");
+
+__global__ __launch_bounds__(256) void dino_attention_kernel(const float* __restrict__ qkv, float* __restrict__ ao, float* __restrict__ row0) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* Qs = lds;                    // [32][LDQ]
+    float* KVs = Qs + QT * LDQ;         // K [197][LDK], later V [200][LDV]
+    float* Ps = KVs + KV_FLOATS;        // scores, then probabilities [32][LDP]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q0 = blockIdx.x * QT, h = blockIdx.y, b = blockIdx.z;
+    const float* base = qkv + (size_t)b * T * 3 * D + h * HD;
+    for (int i = tid; i < QT * (HD / 4); i += 256) {   // query rows past 196 repeat row 196; their results are never stored
+        const int r = i >> 4, c = (i & 15) * 4;
+        const float4 v = *reinterpret_cast<const float4*>(base + (size_t)min(q0 + r, T - 1) * 3 * D + c);
+        float* d = Qs + r * LDQ + c;
+        d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+    }
+    for (int i = tid; i < T * (HD / 4); i += 256) {
+        const int r = i >> 4, c = (i & 15) * 4;
+        const float4 v = *reinterpret_cast<const float4*>(base + (size_t)r * 3 * D + D + c);
+        float* d = KVs + r * LDK + c;
+        d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+    }
+    __syncthreads();
+    // scores: 13 column tiles of 16 keys (the last: keys 192..207, clamped to 196 and masked below), both 16-row halves per wave
+    const int li = lane & 15, lk = lane >> 4;
+    for (int tj = wave; tj < 13; tj += 4) {
+        f32x4 s0 = {0.0f, 0.0f, 0.0f, 0.0f}, s1 = s0;
+        const float* qa = Qs + li * LDQ + lk;
+        const float* kb = KVs + min(tj * 16 + li, T - 1) * LDK + lk;
+#pragma unroll
+        for (int k0 = 0; k0 < HD; k0 += 4) {   // d ascending
+            const float bb = kb[k0];
+            s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[k0], bb, s0, 0, 0, 0);
+            s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[16 * LDQ + k0], bb, s1, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {   // C/D: col = lane & 15, row = 4 * (lane >> 4) + r
+            Ps[(lk * 4 + r) * LDP + tj * 16 + li] = s0[r] * 0.125f;   // scale = 64^-0.5
+            Ps[(16 + lk * 4 + r) * LDP + tj * 16 + li] = s1[r] * 0.125f;
+        }
+    }
+    __syncthreads();   // K is dead from here: V takes its place
+    for (int i = tid; i < TP * (HD / 4); i += 256) {
+        const int r = i >> 4, c = (i & 15) * 4;
+        float4 v = {0.0f, 0.0f, 0.0f, 0.0f};   // keys 197..199: zero rows under zero probabilities
+        if (r < T) v = *reinterpret_cast<const float4*>(base + (size_t)r * 3 * D + 2 * D + c);
+        *reinterpret_cast<float4*>(KVs + r * LDV + c) = v;
+    }
+    // softmax with the row maximum subtracted: wave w owns rows 8w..8w+7, a lane the columns lane, lane+64, lane+128, lane+192
+    for (int r = wave * 8; r < wave * 8 + 8; ++r) {
+        float* pr = Ps + r * LDP;
+        float v[4], m = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = lane + 64 * j;
+            v[j] = c < T ? pr[c] : -INFINITY;
+            m = fmaxf(m, v[j]);
+        }
+        m = dino_wave_max(m);
+        float s = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[j] = (lane + 64 * j) < T ? expf(v[j] - m) : 0.0f;
+            s += v[j];
+        }
+        s = dino_wave_sum(s);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = lane + 64 * j;
+            if (c < TP) pr[c] = v[j] / s;
+        }
+    }
+    __syncthreads();
+    if (row0 && q0 == 0 && tid < NP) row0[((size_t)b * HEADS + h) * NP + tid] = Ps[1 + tid];   // block 11: row 0, columns 1..196
+    // out = P V: wave w owns output columns 16w..16w+15, both row halves; keys ascending
+    {
+        f32x4 o0 = {0.0f, 0.0f, 0.0f, 0.0f}, o1 = o0;
+        const float* pa = Ps + li * LDP + lk;
+        const float* vb = KVs + lk * LDV + wave * 16 + li;
+#pragma unroll 10
+        for (int k0 = 0; k0 < TP; k0 += 4) {
+            const float bb = vb[k0 * LDV];
+            o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[k0], bb, o0, 0, 0, 0);
+            o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[16 * LDP + k0], bb, o1, 0, 0, 0);
+        }
+        float* dst = ao + (size_t)b * T * D + h * HD + wave * 16 + li;   // (attn @ v).transpose(1, 2).reshape(B, N, C)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ra = q0 + lk * 4 + r, rb = ra + 16;
+            if (ra < T) dst[(size_t)ra * D] = o0[r];
+            if (rb < T) dst[(size_t)rb * D] = o1[r];
+        }
+    }
+}
+
+// ---- outputs: cls = x[:,0], feat = x[:,1:], attn = mean over the heads (0..5 in order) of the saved row 0 ----------------------
+__global__ __launch_bounds__(256) void dino_outputs_kernel(const float* __restrict__ x, const float* __restrict__ row0, int batch,
+                                                           float* __restrict__ feat, float* __restrict__ cls, float* __restrict__ attn) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)batch * T * D) return;
+    const int c = (int)(e % D), t = (int)((e / D) % T), b = (int)(e / ((long long)T * D));
+    const float v = x[e];
+    if (t == 0) {
+        if (cls) cls[(size_t)b * D + c] = v;
+        if (attn && row0)
+            for (int j = c; j < NP; j += D) {
+                float s = 0.0f;
+                for (int h = 0; h < HEADS; ++h) s += row0[((size_t)b * HEADS + h) * NP + j];
+                attn[(size_t)b * NP + j] = s / (float)HEADS;
+            }
+    } else if (feat) {
+        feat[((size_t)b * NP + t - 1) * D + c] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void dino_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e < n) dst[e] = src[e];
+}
+// dst[i][o] = src[o][i]  (nn.Linear [out,in] -> the GEMM's [in,out])
+__global__ __launch_bounds__(256) void dino_transpose_kernel(const float* __restrict__ src, float* __restrict__ dst, int n_out, int n_in) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)n_out * n_in) return;
+    const int o = (int)(e % n_out), i = (int)(e / n_out);
+    dst[e] = src[(size_t)o * n_in + i];
+}
+__global__ __launch_bounds__(256) void dino_add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ dst, int n) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < n) dst[e] = a[e] + b[e];
+}
+
+inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
+
+template <int EPI, int K>
+void launch_gemm(const float* A, const float* Wt, const float* bias, float* out, const float* extra, int M, int N, hipStream_t st) {
+    static_assert(K % GK == 0, "GEMM tiles");
+    dino_gemm_kernel<EPI, K><<<dim3(N / GN, (M + GM - 1) / GM), 256, 0, st>>>(A, Wt, bias, out, extra, M, N);
+}
+
+// The attention kernel's 99 KB of dynamic LDS needs the attribute once per device.  nsos_dino_pack sets it too, so a forward call
+// that is the first one inside a stream capture finds it done.
+int32_t dino_configure() {
+    static NsosPerDeviceFlag configured;
+    if (!configured.here()) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dino_attention_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           ATT_LDS_BYTES);
+        if (e != hipSuccess) return (int32_t)e;
+        configured.here() = true;
+    }
+    return NSOS_OK;
+}
+static_assert(D % GN == 0 && (3 * D) % GN == 0 && HID % GN == 0 && D % GK == 0 && KE % GK == 0 && HID % GK == 0, "GEMM tiles");
+
+}  // namespace
+
+extern "C" size_t nsos_dino_packed_bytes(void) { return P_SIZE * sizeof(float); }
+
+extern "C" size_t nsos_dino_workspace_bytes(int32_t batch) {
+    return (batch >= 1 && batch <= NSOS_DINO_MAX_BATCH) ? (size_t)batch * W_SIZE * sizeof(float) : 0;
+}
+
+extern "C" int32_t nsos_dino_resize_indices(int32_t in_size, int32_t patch_stride, int32_t* idx) {
+    NSOS_REQUIRE(idx, NSOS_ERR_NULL_POINTER);
+    NSOS_REQUIRE(in_size > 0, NSOS_ERR_BAD_SHAPE);
+    NSOS_REQUIRE(in_size <= (1 << 14) && patch_stride <= (1 << 10), NSOS_ERR_UNSUPPORTED);
+    for (int i = 0; i < IMG; ++i) idx[i] = dino_source_index(i, in_size, patch_stride);
+    return NSOS_OK;
+}
+
+extern "C" int32_t nsos_dino_pack(const nsos_dino_tensors* t, void* packed, size_t packed_bytes, void* stream) {
+    NSOS_REQUIRE(t && packed, NSOS_ERR_NULL_POINTER);
+    NSOS_REQUIRE(t->cls_token && t->pos_embed && t->patch_w && t->patch_b, NSOS_ERR_NULL_POINTER);
+    for (int i = 0; i < NSOS_DINO_DEPTH; ++i) {
+        const nsos_dino_block_tensors& b = t->blocks[i];
+        NSOS_REQUIRE(b.norm1_w && b.norm1_b && b.qkv_w && b.qkv_b && b.proj_w && b.proj_b && b.norm2_w && b.norm2_b && b.fc1_w &&
+                         b.fc1_b && b.fc2_w && b.fc2_b,
+                     NSOS_ERR_NULL_POINTER);
+    }
+    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0, NSOS_ERR_MISALIGNED);
+    NSOS_REQUIRE(packed_bytes >= P_SIZE * sizeof(float), NSOS_ERR_BUFFER_TOO_SMALL);
+    if (int32_t c = dino_configure()) return c;
+    hipStream_t st = (hipStream_t)stream;
+    float* p = (float*)packed;
+    auto copy = [&](const float* src, float* dst, long long n) { dino_copy_kernel<<<blocks_for(n), 256, 0, st>>>(src, dst, n); };
+    auto transpose = [&](const float* src, float* dst, int n_out, int n_in) {
+        dino_transpose_kernel<<<blocks_for((long long)n_out * n_in), 256, 0, st>>>(src, dst, n_out, n_in);
+    };
+    copy(t->pos_embed + D, p + P_POS + D, (long long)NP * D);
+    dino_add_kernel<<<blocks_for(D), 256, 0, st>>>(t->cls_token, t->pos_embed, p + P_POS, D);
+    transpose(t->patch_w, p + P_EMB_W, D, KE);
+    copy(t->patch_b, p + P_EMB_B, D);
+    for (int i = 0; i < NSOS_DINO_DEPTH; ++i) {
+        const nsos_dino_block_tensors& b = t->blocks[i];
+        float* q = p + P_BLOCKS + (size_t)i * B_SIZE;
+        copy(b.norm1_w, q + B_LN1W, D), copy(b.norm1_b, q + B_LN1B, D);
+        transpose(b.qkv_w, q + B_QKVW, 3 * D, D), copy(b.qkv_b, q + B_QKVB, 3 * D);
+        transpose(b.proj_w, q + B_PROJW, D, D), copy(b.proj_b, q + B_PROJB, D);
+        copy(b.norm2_w, q + B_LN2W, D), copy(b.norm2_b, q + B_LN2B, D);
+        transpose(b.fc1_w, q + B_FC1W, HID, D), copy(b.fc1_b, q + B_FC1B, HID);
+        transpose(b.fc2_w, q + B_FC2W, D, HID), copy(b.fc2_b, q + B_FC2B, D);
+    }
+    return nsos_launch_status();
+}
+
+extern "C" int32_t nsos_dino_forward(const float* input, int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags,
+                                     const void* packed, void* workspace, size_t workspace_bytes, float* feat, float* cls, float* attn,
+                                     float* prepared, float* blocks, void* stream) {
+    NSOS_REQUIRE(input && packed && workspace, NSOS_ERR_NULL_POINTER);
+    NSOS_REQUIRE(batch > 0 && in_h > 0 && in_w > 0, NSOS_ERR_BAD_SHAPE);
+    NSOS_REQUIRE((flags & ~7) == 0, NSOS_ERR_UNSUPPORTED);
+    if (flags & NSOS_DINO_PREPARED) {
+        NSOS_REQUIRE(flags == NSOS_DINO_PREPARED, NSOS_ERR_UNSUPPORTED);
+        NSOS_REQUIRE(in_h == IMG && in_w == IMG, NSOS_ERR_BAD_SHAPE);
+    }
+    if (flags & NSOS_DINO_STEP1) {
+        NSOS_REQUIRE(patch_stride > 0, NSOS_ERR_BAD_SHAPE);   // an intermediate image of extent 0
+        NSOS_REQUIRE(patch_stride <= (1 << 10), NSOS_ERR_UNSUPPORTED);
+    }
+    NSOS_REQUIRE(batch <= NSOS_DINO_MAX_BATCH && in_h <= (1 << 14) && in_w <= (1 << 14), NSOS_ERR_UNSUPPORTED);
+    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)input & 3) == 0, NSOS_ERR_MISALIGNED);
+    NSOS_REQUIRE(workspace_bytes >= nsos_dino_workspace_bytes(batch), NSOS_ERR_BUFFER_TOO_SMALL);
+
+    if (int32_t c = dino_configure()) return c;
+    hipStream_t st = (hipStream_t)stream;
+    const float* p = (const float*)packed;
+    float* ws = (float*)workspace;
+    const size_t Bn = (size_t)batch;
+    float *x = ws + Bn * W_X, *ln = ws + Bn * W_LN, *qkv = ws + Bn * W_QKV, *ao = ws + Bn * W_AO, *hid = ws + Bn * W_HID,
+          *tok = ws + Bn * W_TOK, *row0 = ws + Bn * W_ROW0;
+    const int M = batch * T;
+
+    dino_prepare_kernel<<<blocks_for((long long)batch * NP * KE), 256, 0, st>>>(input, batch, in_h, in_w, patch_stride, flags, p + P_POS, tok, x,
+                                                                                prepared);
+    launch_gemm<EPI_EMBED, KE>(tok, p + P_EMB_W, p + P_EMB_B, x, p + P_POS, batch * NP, D, st);
+    for (int i = 0; i < NSOS_DINO_DEPTH; ++i) {
+        const float* q = p + P_BLOCKS + (size_t)i * B_SIZE;
+        dino_layernorm_kernel<<<(M + 3) / 4, 256, 0, st>>>(x, q + B_LN1W, q + B_LN1B, ln, M);
+        launch_gemm<EPI_BIAS, D>(ln, q + B_QKVW, q + B_QKVB, qkv, nullptr, M, 3 * D, st);
+        dino_attention_kernel<<<dim3((T + QT - 1) / QT, HEADS, batch), 256, ATT_LDS_BYTES, st>>>(
+            qkv, ao, (i == NSOS_DINO_DEPTH - 1 && attn) ? row0 : nullptr);
+        launch_gemm<EPI_RESIDUAL, D>(ao, q + B_PROJW, q + B_PROJB, x, x, M, D, st);
+        dino_layernorm_kernel<<<(M + 3) / 4, 256, 0, st>>>(x, q + B_LN2W, q + B_LN2B, ln, M);
+        launch_gemm<EPI_GELU, D>(ln, q + B_FC1W, q + B_FC1B, hid, nullptr, M, HID, st);
+        launch_gemm<EPI_RESIDUAL, HID>(hid, q + B_FC2W, q + B_FC2B, x, x, M, D, st);
+        if (blocks) dino_copy_kernel<<<blocks_for((long long)M * D), 256, 0, st>>>(x, blocks + (size_t)i * M * D, (long long)M * D);
+    }
+    if (feat || cls || attn)
+        dino_outputs_kernel<<<blocks_for((long long)M * D), 256, 0, st>>>(x, attn ? row0 : nullptr, batch, feat, cls, attn);
+    return nsos_launch_status();
+}

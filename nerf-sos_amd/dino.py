@@ -1,0 +1,137 @@
+"""The frozen DINO ViT-S/16 feature extractor of the NeRF-SOS training step on the HIP kernels of csrc/dino_vit.hip.
+
+Drop-in for the reference's `VitExtractor` as the trainer uses it (models/extractor.py:204-213 `get_vit_attn_feat`, called from
+engines/trainer.py:101-109): the parameters carry the names and shapes of DINO's own checkpoint, so
+`DinoViT().load_state_dict(torch.load("dino_deitsmall16_pretrain.pth"))` takes the file `torch.hub` would have fetched.  Nothing
+here downloads anything.  Forward only (the reference never trains DINO); there is no CPU path.
+"""
+from __future__ import annotations
+
+from typing import Dict
+
+import torch
+import torch.nn as nn
+
+from . import ops
+
+DEPTH, WIDTH, HEADS, TOKENS, HIDDEN, PATCH, IMAGE = 12, 384, 6, 197, 1536, 16, 224
+
+
+class _Affine(nn.Module):
+    """A weight / bias pair under the checkpoint's name (nn.Linear, nn.LayerNorm or the patch convolution): storage only."""
+
+    def __init__(self, w_shape, b_shape, ones=False):
+        super().__init__()
+        w = torch.ones(w_shape) if ones else nn.init.trunc_normal_(torch.empty(w_shape), std=0.02)
+        self.weight = nn.Parameter(w, requires_grad=False)
+        self.bias = nn.Parameter(torch.zeros(b_shape), requires_grad=False)
+
+
+class _Attn(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.qkv = _Affine((3 * WIDTH, WIDTH), (3 * WIDTH,))
+        self.proj = _Affine((WIDTH, WIDTH), (WIDTH,))
+
+
+class _Mlp(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.fc1 = _Affine((HIDDEN, WIDTH), (HIDDEN,))
+        self.fc2 = _Affine((WIDTH, HIDDEN), (WIDTH,))
+
+
+class _Block(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.norm1 = _Affine((WIDTH,), (WIDTH,), ones=True)
+        self.attn = _Attn()
+        self.norm2 = _Affine((WIDTH,), (WIDTH,), ones=True)
+        self.mlp = _Mlp()
+
+
+class _PatchEmbed(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.proj = _Affine((WIDTH, 3, PATCH, PATCH), (WIDTH,))
+
+
+class DinoViT(nn.Module):
+    """vit_small(patch_size=16) of models/vision_transformer.py, frozen.  150 state-dict tensors under DINO's names; `norm.*` is
+    loaded and never applied (the reference reads block 11's output before the final norm)."""
+
+    def __init__(self):
+        super().__init__()
+        self.cls_token = nn.Parameter(nn.init.trunc_normal_(torch.empty(1, 1, WIDTH), std=0.02), requires_grad=False)
+        self.pos_embed = nn.Parameter(nn.init.trunc_normal_(torch.empty(1, TOKENS, WIDTH), std=0.02), requires_grad=False)
+        self.patch_embed = _PatchEmbed()
+        self.blocks = nn.ModuleList([_Block() for _ in range(DEPTH)])
+        self.norm = _Affine((WIDTH,), (WIDTH,), ones=True)
+        self._packed = None
+        self._packed_key = None
+        self._workspace = {}
+        self._retired = []
+
+    # ---- packed weights: once, and again when a parameter's storage or version changed (the pattern of NeRFMLP.packed_weights)
+    def _key(self):
+        # 150 (data_ptr, _version) pairs per call: a few tens of microseconds of host time, inside every eager timing
+        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+
+    def packed_weights(self) -> torch.Tensor:
+        key = self._key()
+        if self._packed is None or key != self._packed_key or self._packed.device != self.cls_token.device:
+            if not self.cls_token.is_cuda:
+                raise RuntimeError("nerf_sos_amd: DinoViT must live on a GPU -- this package has no CPU path")
+            reuse = self._packed if self._packed is not None and self._packed.device == self.cls_token.device else None
+            self._packed = ops.dino_pack(dict(self.named_parameters()), reuse)
+            self._packed_key = key
+        return self._packed
+
+    def invalidate_packed(self):
+        self._packed_key = None
+
+    def _ws(self, batch: int, device) -> torch.Tensor:
+        """ONE workspace per device, grown to the largest batch seen (3.6 MB per image) and reused by every call, so that a
+        captured call keeps valid pointers.  Calls of one module on DIFFERENT streams at the same time would race on it: give each
+        stream its own DinoViT (the packed weights are small) or order the streams."""
+        key = str(device)
+        ws = self._workspace.get(key)
+        if ws is None or ws.numel() < ops.dino_workspace_floats(batch):
+            if ws is not None:
+                self._retired.append(ws)      # a graph captured at the smaller batch still points into it
+            ws = self._workspace[key] = ops.dino_workspace(batch, device)
+        return ws
+
+    def _run(self, x, flags, patch_stride=0, **want) -> Dict[str, torch.Tensor]:
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError("nerf_sos_amd: DinoViT needs a GPU tensor -- this package has no CPU path")
+        packed = self.packed_weights()
+        with torch.no_grad():
+            return ops.dino_forward(x.detach(), packed, flags, patch_stride, self._ws(int(x.shape[0]), x.device), **want)
+
+    # ---- the reference's interface
+    def get_vit_attn_feat(self, x: torch.Tensor, prepared: bool = False, **want) -> Dict[str, torch.Tensor]:
+        """models/extractor.py:204-213: x [B,3,h,w] -> nearest resize to 224x224, (x - mean) / std, the network;
+        {'attn' [B,1,196], 'cls_' [B,384], 'feat' [B,196,384]}.  prepared=True: x is the [B,3,224,224] network input itself."""
+        if prepared:
+            if tuple(x.shape[1:]) != (3, IMAGE, IMAGE):
+                raise ValueError(f"a prepared input is [B,3,{IMAGE},{IMAGE}], got {tuple(x.shape)}")
+            return self._run(x, ops.DINO_PREPARED, **want)
+        return self._run(x, 0, **want)
+
+    def patch_features(self, rgb: torch.Tensor, patch_stride: int, **want) -> Dict[str, torch.Tensor]:
+        """engines/trainer.py:103-109 from the rendered patches: rgb [B,P,P,3] (or [B,3,P,P]) -> resize to P*stride, normalise,
+        then get_vit_attn_feat (which resizes to 224 and normalises again).  Returns get_vit_attn_feat's dict plus 'feats'
+        [B,384,14,14] (the trainer's permuted view of 'feat': CorrelationLoss' orig_feats) and 'cls_tokens' (= 'cls_': similarity_negatives /
+        NeRFContrastive)."""
+        if patch_stride < 1:
+            raise ValueError(f"patch_stride must be >= 1, got {patch_stride}")
+        nhwc = rgb.dim() == 4 and rgb.shape[-1] == 3 and rgb.shape[1] != 3
+        out = self._run(rgb, ops.DINO_STEP1 | (ops.DINO_NHWC if nhwc else 0), int(patch_stride), **want)
+        B = out["feat"].shape[0]
+        out["feats"] = out["feat"].reshape(B, 14, 14, WIDTH).permute(0, 3, 1, 2)   # engines/trainer.py:136-137
+        out["cls_tokens"] = out["cls_"]
+        return out
+
+    def forward(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        return self.get_vit_attn_feat(x)

@@ -1139,3 +1139,109 @@ def relu_mask_(g: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
         raise ValueError("relu_mask_: shape mismatch")
     _lib.check(_lib.lib().nsos_relu_mask(g.data_ptr(), ldg, h.data_ptr(), ldh, g.shape[0], g.shape[1], _stream()), "nsos_relu_mask")
     return g
+
+
+# ------------------------------------------------------------------------------------------ DINO ViT-S/16 feature extractor
+DINO_NHWC, DINO_STEP1, DINO_PREPARED = 1, 2, 4          # flags of nsos_dino_forward
+DINO_DEPTH, DINO_WIDTH, DINO_TOKENS, DINO_IMAGE = 12, 384, 197, 224
+_DINO_SHAPES = {"cls_token": (1, 1, 384), "pos_embed": (1, 197, 384), "patch_embed.proj.weight": (384, 3, 16, 16),
+                "patch_embed.proj.bias": (384,), "norm1.weight": (384,), "norm1.bias": (384,), "attn.qkv.weight": (1152, 384),
+                "attn.qkv.bias": (1152,), "attn.proj.weight": (384, 384), "attn.proj.bias": (384,), "norm2.weight": (384,),
+                "norm2.bias": (384,), "mlp.fc1.weight": (1536, 384), "mlp.fc1.bias": (1536,), "mlp.fc2.weight": (384, 1536),
+                "mlp.fc2.bias": (384,)}
+
+
+def _dino_buffer(t: torch.Tensor, name: str, nbytes: int, device) -> torch.Tensor:
+    """A kernel-side buffer: a contiguous float32 GPU tensor on `device` of at least nbytes."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        raise RuntimeError(f"nerf_sos_amd: dino `{name}` must be a contiguous float32 GPU tensor -- this package has no CPU path")
+    if t.device != device:
+        raise RuntimeError(f"dino: `{name}` is on {t.device}, the data on {device}")
+    if t.numel() * 4 < nbytes:
+        raise ValueError(f"dino: `{name}` holds {t.numel() * 4} bytes, {nbytes} needed")
+    return t
+_DINO_BLOCK_FIELDS = (("norm1_w", "norm1.weight"), ("norm1_b", "norm1.bias"), ("qkv_w", "attn.qkv.weight"), ("qkv_b", "attn.qkv.bias"),
+                      ("proj_w", "attn.proj.weight"), ("proj_b", "attn.proj.bias"), ("norm2_w", "norm2.weight"), ("norm2_b", "norm2.bias"),
+                      ("fc1_w", "mlp.fc1.weight"), ("fc1_b", "mlp.fc1.bias"), ("fc2_w", "mlp.fc2.weight"), ("fc2_b", "mlp.fc2.bias"))
+
+
+def dino_pack(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """DINO's checkpoint tensors (state-dict names, on one GPU) -> the stream nsos_dino_forward reads (`nsos_dino_pack`)."""
+    keep = []
+
+    def ptr(name):
+        t = _dev(state[name].detach(), name)
+        want = _DINO_SHAPES[name.split(".", 2)[2] if name.startswith("blocks.") else name]
+        if tuple(t.shape) != want:                      # the pack kernels read exactly these extents
+            raise ValueError(f"dino: `{name}` has shape {tuple(t.shape)}, the checkpoint's is {want}")
+        if keep and t.device != keep[0].device:
+            raise RuntimeError(f"dino: `{name}` is on {t.device}, the other tensors on {keep[0].device}")
+        keep.append(t)
+        return t.data_ptr()
+
+    ts = _lib.DinoTensors()
+    ts.cls_token, ts.pos_embed = ptr("cls_token"), ptr("pos_embed")
+    ts.patch_w, ts.patch_b = ptr("patch_embed.proj.weight"), ptr("patch_embed.proj.bias")
+    for i in range(DINO_DEPTH):
+        for field, name in _DINO_BLOCK_FIELDS:
+            setattr(ts.blocks[i], field, ptr(f"blocks.{i}.{name}"))
+    nbytes = int(_lib.lib().nsos_dino_packed_bytes())
+    if packed is None:
+        packed = torch.empty((nbytes // 4,), device=keep[0].device, dtype=torch.float32)
+    _dino_buffer(packed, "packed", nbytes, keep[0].device)
+    with torch.cuda.device(packed.device):
+        _lib.check(_lib.lib().nsos_dino_pack(C.byref(ts), _p(packed), packed.numel() * 4, _stream()), "nsos_dino_pack")
+    return packed
+
+
+def dino_workspace_floats(batch: int) -> int:
+    nbytes = int(_lib.lib().nsos_dino_workspace_bytes(int(batch)))
+    if nbytes == 0:
+        raise ValueError(f"dino: batch size {batch} outside what the kernels take")
+    return nbytes // 4
+
+
+def dino_workspace(batch: int, device) -> torch.Tensor:
+    return torch.empty((dino_workspace_floats(batch),), device=device, dtype=torch.float32)
+
+
+def dino_forward(x: torch.Tensor, packed: torch.Tensor, flags: int, patch_stride: int = 0, workspace: Optional[torch.Tensor] = None,
+                 want_attn: bool = True, want_prepared: bool = False, want_blocks: bool = False) -> Dict[str, torch.Tensor]:
+    """`nsos_dino_forward`: x [B,h,w,3] (DINO_NHWC) or [B,3,h,w] -> {'feat' [B,196,384], 'cls_' [B,384], 'attn' [B,1,196]}
+    (+ 'prepared' [B,3,224,224], 'blocks' [12,B,197,384] on request).  Launches only; capturable."""
+    x = _dev(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"dino: expected a 4-d image batch, got {tuple(x.shape)}")
+    B = int(x.shape[0])
+    h, w, ch = (int(x.shape[1]), int(x.shape[2]), int(x.shape[3])) if flags & DINO_NHWC else (int(x.shape[2]), int(x.shape[3]), int(x.shape[1]))
+    if ch != 3:
+        raise ValueError(f"dino: expected 3 channels, got {tuple(x.shape)}")
+    dev = x.device
+    if workspace is None:
+        workspace = dino_workspace(B, dev)
+    _dino_buffer(packed, "packed", int(_lib.lib().nsos_dino_packed_bytes()), dev)
+    nws = int(_lib.lib().nsos_dino_workspace_bytes(B))
+    if nws == 0:
+        raise ValueError(f"dino: batch size {B} outside what the kernels take")
+    _dino_buffer(workspace, "workspace", nws, dev)
+    out = {"feat": torch.empty((B, DINO_TOKENS - 1, DINO_WIDTH), device=dev, dtype=torch.float32),
+           "cls_": torch.empty((B, DINO_WIDTH), device=dev, dtype=torch.float32)}
+    if want_attn:
+        out["attn"] = torch.empty((B, 1, DINO_TOKENS - 1), device=dev, dtype=torch.float32)
+    if want_prepared:
+        out["prepared"] = torch.empty((B, 3, DINO_IMAGE, DINO_IMAGE), device=dev, dtype=torch.float32)
+    if want_blocks:
+        out["blocks"] = torch.empty((DINO_DEPTH, B, DINO_TOKENS, DINO_WIDTH), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nsos_dino_forward(_p(x), B, h, w, int(patch_stride), int(flags), _p(packed), _p(workspace), workspace.numel() * 4,
+                                                _p(out["feat"]), _p(out["cls_"]), _p(out.get("attn")), _p(out.get("prepared")),
+                                                _p(out.get("blocks")), _stream()), "nsos_dino_forward")
+    return out
+
+
+def dino_resize_indices(in_size: int, patch_stride: int = 0):
+    """The source index of each of the 224 rows / columns after the trainer's and the extractor's nearest resizes (host; the rule
+    the prepare kernel evaluates).  patch_stride 0: the extractor's resize alone."""
+    idx = (C.c_int32 * DINO_IMAGE)()
+    _lib.check(_lib.lib().nsos_dino_resize_indices(int(in_size), int(patch_stride), idx), "nsos_dino_resize_indices")
+    return list(idx)

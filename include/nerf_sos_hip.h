@@ -788,6 +788,44 @@ int32_t nsos_dino_forward(const float* input, int32_t batch, int32_t in_h, int32
  * (patch_stride <= 0: step 2 alone), exactly the rule the prepare kernel evaluates.  idx: HOST int32 [224]. */
 int32_t nsos_dino_resize_indices(int32_t in_size, int32_t patch_stride, int32_t* idx);
 
+/* ---- DINO's full-image path and find_fg (engines/eval.py:133-144 and :237-248) ---------------------------------------------
+ * models/extractor.py:215-224 get_vit_attn_feat_noresize: x [B,3,H,W] (or [B,H,W,3] with NSOS_DINO_FULL_NHWC), (x - mean) / std
+ * once (twice with NSOS_DINO_FULL_NORMALIZE: eval.py's normalize_batch first), no resize; a rows x cols = (H // 16) x (W // 16)
+ * patch grid (the remainder pixels are never read), T = 1 + rows*cols tokens; every H, W >= 16 with rows*cols <= 16384.
+ * Position embedding (models/vision_transformer.py:174-194): used as it is when rows*cols == 196 and H == W; otherwise the 14x14
+ * patch part goes through ATen's upsample_bicubic2d (align_corners=False, A = -0.75, border taps clamped) with
+ * scale_factor = ((rows + 0.1) / 14, (cols + 0.1) / 14) -- source coordinate (dst + 0.5) / scale_factor - 0.5 --, evaluated in fp64
+ * and rounded once; the class position is prepended unchanged.  Then the same 12 blocks (same GEMM and LayerNorm kernels, same
+ * orders as nsos_dino_forward) with a streaming attention: keys in tiles of 64, ascending, running max m and sum l per query row
+ * (online softmax: per tile the row max / sum over a lane's four 16-key blocks in order, then an xor butterfly 1,2,4,8 over the
+ * row's 16 lanes; o and l rescaled by exp(m_old - m_new); q.k over d = 0..63 ascending; p.v over the tile's keys ascending; o / l at
+ * the end).  attn = block 11's softmax of query 0, exp(s - m) / l per head with that head's final (m, l), heads 0..5 summed in
+ * order, / 6.  Outputs, each optional: feat [B,rows*cols,384], cls [B,384], attn [B,1,rows*cols], pos [T,384] (the table added to
+ * the tokens).  Workspace: nsos_dino_full_workspace_bytes(batch, H, W) bytes, 16-byte aligned; 0 = refused (batch outside
+ * 1..NSOS_DINO_MAX_BATCH, H or W < 16, over the token cap, batch*T over the GEMMs' grid, or a size past size_t).  Everything is
+ * validated before anything is launched; no host synchronisation, no allocation: capturable. */
+#define NSOS_DINO_FULL_MAX_PATCHES 16384
+enum {
+    NSOS_DINO_FULL_NHWC = 1,      /* input [B,H,W,3] (the renderer's rgb) instead of [B,3,H,W] */
+    NSOS_DINO_FULL_NORMALIZE = 2  /* normalise twice: engines/eval.py:136 normalize_batch, then get_vit_attn_feat_noresize's own */
+};
+size_t nsos_dino_full_workspace_bytes(int32_t batch, int32_t h, int32_t w);
+int32_t nsos_dino_forward_full(const float* input, int32_t batch, int32_t h, int32_t w, int32_t flags, const void* packed,
+                               void* workspace, size_t workspace_bytes, float* feat, float* cls, float* attn, float* pos, void* stream);
+/* Host helper: the position table [1 + rows*cols][384] the forward adds, from a HOST pos_embed [197][384] (row 0 copied), by the
+ * rule the kernel evaluates.  out: HOST float [(1 + rows*cols) * 384]. */
+int32_t nsos_dino_interp_pos(const float* pos_embed, int32_t h, int32_t w, float* out);
+/* find_fg (engines/eval.py:138-144) for one image: attn [rows*cols] (the forward's attn of that image) nearest-upsampled to H x W
+ * by ATen's size= rule min(floor(dst * (float)rows / H), rows - 1); over labels [H*W] (int32, e.g. the k-means clustering
+ * [H,W,1]) the sums of the upsampled attention and the pixel counts of clusters 0 and 1, in fp64: 256 fixed pixel ranges, each a
+ * strided per-thread sum then a tree 128,64,..,1, then the same tree over the 256 partials.  mean = sum / count (an empty cluster
+ * gives NaN); flipped = mean1 < mean0 (False with a NaN); out_labels = flipped ? 1 - labels : labels for every pixel (labels
+ * outside {0,1} enter neither mean but are mapped: 2 -> -1).  Optional outputs: attn_up [H*W] fp32, means [2] fp64
+ * (mean0, mean1), flipped [1] int32.  workspace: nsos_dino_find_fg_workspace_bytes(), 16-byte aligned.  No host synchronisation. */
+size_t nsos_dino_find_fg_workspace_bytes(void);
+int32_t nsos_dino_find_fg(const int32_t* labels, const float* attn, int32_t h, int32_t w, int32_t* out_labels, float* attn_up,
+                          double* means, int32_t* flipped, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

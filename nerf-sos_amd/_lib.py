@@ -149,6 +149,11 @@ SIGNATURES = {
     "nsos_dino_workspace_bytes": (_sz, [_i32]),
     "nsos_dino_forward": (_i32, [_fp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _fp]),
     "nsos_dino_resize_indices": (_i32, [_i32, _i32, C.POINTER(C.c_int32)]),
+    "nsos_dino_full_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "nsos_dino_forward_full": (_i32, [_fp, _i32, _i32, _i32, _i32, _fp, _fp, _sz, _fp, _fp, _fp, _fp, _fp]),
+    "nsos_dino_interp_pos": (_i32, [C.POINTER(C.c_float), _i32, _i32, C.POINTER(C.c_float)]),
+    "nsos_dino_find_fg_workspace_bytes": (_sz, []),
+    "nsos_dino_find_fg": (_i32, [_fp, _fp, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
     "nsos_corr_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "nsos_app_correlation_loss": (_i32, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                          _f32, _f32, _f32, _f32, _fp, _fp, _fp, _sz, _fp]),

@@ -70,6 +70,7 @@ class DinoViT(nn.Module):
         self._packed = None
         self._packed_key = None
         self._workspace = {}
+        self._workspace_full = {}
         self._retired = []
 
     # ---- packed weights: once, and again when a parameter's storage or version changed (the pattern of NeRFMLP.packed_weights)
@@ -102,6 +103,28 @@ class DinoViT(nn.Module):
             ws = self._workspace[key] = ops.dino_workspace(batch, device)
         return ws
 
+    def _ws_full(self, batch: int, h: int, w: int, device) -> torch.Tensor:
+        """The full-image path's workspace: ONE per device, grown to the largest need seen (the layout of a smaller (B, rows, cols)
+        fits in a larger buffer) and reused by every call, so that a captured call keeps valid pointers (the pattern of _ws)."""
+        key = str(device)
+        ws = self._workspace_full.get(key)
+        need = ops.dino_full_workspace_floats(batch, h, w)
+        if ws is None or ws.numel() < need:
+            if ws is not None:
+                self._retired.append(ws)      # a graph captured at the smaller size still points into it
+            ws = self._workspace_full[key] = torch.empty((need,), device=device, dtype=torch.float32)
+        return ws
+
+    def _run_full(self, x, flags, **want) -> Dict[str, torch.Tensor]:
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError("nerf_sos_amd: DinoViT needs a GPU tensor -- this package has no CPU path")
+        if x.dim() != 4:
+            raise ValueError(f"dino: expected a 4-d image batch, got {tuple(x.shape)}")
+        h, w = (int(x.shape[1]), int(x.shape[2])) if flags & ops.DINO_FULL_NHWC else (int(x.shape[2]), int(x.shape[3]))
+        packed = self.packed_weights()
+        with torch.no_grad():
+            return ops.dino_forward_full(x.detach(), packed, flags, self._ws_full(int(x.shape[0]), h, w, x.device), **want)
+
     def _run(self, x, flags, patch_stride=0, **want) -> Dict[str, torch.Tensor]:
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise RuntimeError("nerf_sos_amd: DinoViT needs a GPU tensor -- this package has no CPU path")
@@ -118,6 +141,12 @@ class DinoViT(nn.Module):
                 raise ValueError(f"a prepared input is [B,3,{IMAGE},{IMAGE}], got {tuple(x.shape)}")
             return self._run(x, ops.DINO_PREPARED, **want)
         return self._run(x, 0, **want)
+
+    def get_vit_attn_feat_noresize(self, x: torch.Tensor, **want) -> Dict[str, torch.Tensor]:
+        """models/extractor.py:215-224: x [B,3,H,W] at full resolution -> (x - mean) / std (no resize), the network on the
+        (H // 16) x (W // 16) patch grid with the position embedding interpolated; {'attn' [B,1,rows*cols], 'cls_' [B,384],
+        'feat' [B,rows*cols,384]}.  H, W >= 16 and rows*cols <= 16384."""
+        return self._run_full(x, 0, **want)
 
     def patch_features(self, rgb: torch.Tensor, patch_stride: int, **want) -> Dict[str, torch.Tensor]:
         """engines/trainer.py:103-109 from the rendered patches: rgb [B,P,P,3] (or [B,3,P,P]) -> resize to P*stride, normalise,

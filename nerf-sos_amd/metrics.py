@@ -96,3 +96,21 @@ def patch_metrics(semantics: torch.Tensor, masks: torch.Tensor, N_cluster: int =
     c = ops.adjusted_rand_score(gt, clus.reshape(-1).to(gt.dtype))
     s = ops.adjusted_rand_score(gt, pp["sem"].reshape(-1).to(gt.dtype))
     return {"clus_ari": c[0], "clus_ari_fg": c[1], "sem_ari": s[0], "sem_ari_fg": s[1], "sem": pp["sem"], "clustering": clus}
+
+
+def find_fg(clustering: torch.Tensor, rgb: torch.Tensor, dino) -> Dict[str, torch.Tensor]:
+    """engines/eval.py:133-144 (and :237-248) on the device: rgb [H,W,3] as rendered -> normalize_batch -> DINO's full-image path
+    (`dino`: a DinoViT) -> the class token's attention nearest-upsampled to [H,W,1]; if its mean over cluster 1 is below its mean
+    over cluster 0, clustering -> 1 - clustering.  clustering: int32 [H,W,1] as view_metrics returns it.  Returns {'clustering'
+    (int32, oriented), 'attn' [H,W,1], 'flipped' (int32 [1])} plus 'means' (float64 [2]: clusters 0, 1); no host synchronisation."""
+    if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda:
+        raise RuntimeError("nerf_sos_amd: find_fg needs a GPU tensor -- this package has no CPU path")
+    if rgb.dim() != 3 or rgb.shape[-1] != 3:
+        raise ValueError(f"find_fg: rgb must be [H,W,3], got {tuple(rgb.shape)}")
+    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    if not isinstance(clustering, torch.Tensor) or tuple(clustering.shape) not in ((H, W, 1), (H, W)):
+        raise ValueError(f"find_fg: clustering must be [{H},{W},1], got {tuple(getattr(clustering, 'shape', ()))}")
+    if clustering.device != rgb.device:
+        raise RuntimeError(f"find_fg: clustering is on {clustering.device}, rgb on {rgb.device}")
+    out = dino._run_full(rgb[None], ops.DINO_FULL_NHWC | ops.DINO_FULL_NORMALIZE)   # eval.py:134-137, fused
+    return ops.dino_find_fg(clustering, out["attn"], H, W)

@@ -1245,3 +1245,94 @@ def dino_resize_indices(in_size: int, patch_stride: int = 0):
     idx = (C.c_int32 * DINO_IMAGE)()
     _lib.check(_lib.lib().nsos_dino_resize_indices(int(in_size), int(patch_stride), idx), "nsos_dino_resize_indices")
     return list(idx)
+
+
+# ---- DINO's full-image path (get_vit_attn_feat_noresize) and find_fg (engines/eval.py:133-144)
+DINO_FULL_NHWC, DINO_FULL_NORMALIZE = 1, 2               # flags of nsos_dino_forward_full
+DINO_FULL_MAX_PATCHES, DINO_PATCH = 16384, 16
+
+
+def dino_full_workspace_floats(batch: int, h: int, w: int) -> int:
+    nbytes = int(_lib.lib().nsos_dino_full_workspace_bytes(int(batch), int(h), int(w)))
+    if nbytes == 0:
+        raise ValueError(f"dino: batch {batch} of {h}x{w} images is outside what the kernels take (H, W >= 16, "
+                         f"(H // 16) * (W // 16) <= {DINO_FULL_MAX_PATCHES}, batch <= 1024)")
+    return nbytes // 4
+
+
+def dino_full_workspace(batch: int, h: int, w: int, device) -> torch.Tensor:
+    return torch.empty((dino_full_workspace_floats(batch, h, w),), device=device, dtype=torch.float32)
+
+
+def dino_forward_full(x: torch.Tensor, packed: torch.Tensor, flags: int = 0, workspace: Optional[torch.Tensor] = None,
+                      want_attn: bool = True, want_pos: bool = False) -> Dict[str, torch.Tensor]:
+    """`nsos_dino_forward_full`: x [B,3,H,W] (or [B,H,W,3] with DINO_FULL_NHWC) at full resolution -> {'attn' [B,1,rows*cols],
+    'cls_' [B,384], 'feat' [B,rows*cols,384]} with rows, cols = H // 16, W // 16 (+ 'pos' [1 + rows*cols, 384] on request).
+    Launches only; capturable."""
+    x = _dev(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"dino: expected a 4-d image batch, got {tuple(x.shape)}")
+    B = int(x.shape[0])
+    h, w, ch = (int(x.shape[1]), int(x.shape[2]), int(x.shape[3])) if flags & DINO_FULL_NHWC else (int(x.shape[2]), int(x.shape[3]), int(x.shape[1]))
+    if ch != 3:
+        raise ValueError(f"dino: expected 3 channels, got {tuple(x.shape)}")
+    dev = x.device
+    nws = dino_full_workspace_floats(B, h, w) * 4
+    if workspace is None:
+        workspace = dino_full_workspace(B, h, w, dev)
+    _dino_buffer(packed, "packed", int(_lib.lib().nsos_dino_packed_bytes()), dev)
+    _dino_buffer(workspace, "workspace", nws, dev)
+    n = (h // DINO_PATCH) * (w // DINO_PATCH)
+    out = {"feat": torch.empty((B, n, DINO_WIDTH), device=dev, dtype=torch.float32),
+           "cls_": torch.empty((B, DINO_WIDTH), device=dev, dtype=torch.float32)}
+    if want_attn:
+        out["attn"] = torch.empty((B, 1, n), device=dev, dtype=torch.float32)
+    if want_pos:
+        out["pos"] = torch.empty((n + 1, DINO_WIDTH), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nsos_dino_forward_full(_p(x), B, h, w, int(flags), _p(packed), _p(workspace), workspace.numel() * 4,
+                                                     _p(out["feat"]), _p(out["cls_"]), _p(out.get("attn")), _p(out.get("pos")),
+                                                     _stream()), "nsos_dino_forward_full")
+    return out
+
+
+def dino_interp_pos(pos_embed, h: int, w: int):
+    """The position table [1 + rows*cols, 384] nsos_dino_forward_full adds, from a CPU pos_embed [1,197,384] (host; the kernel's rule)."""
+    pe = pos_embed.detach().reshape(DINO_TOKENS, DINO_WIDTH).to("cpu", torch.float32).contiguous()
+    n = (int(h) // DINO_PATCH) * (int(w) // DINO_PATCH)
+    out = torch.empty((n + 1, DINO_WIDTH), dtype=torch.float32)
+    fp = C.POINTER(C.c_float)
+    _lib.check(_lib.lib().nsos_dino_interp_pos(C.cast(pe.data_ptr(), fp), int(h), int(w), C.cast(out.data_ptr(), fp)), "nsos_dino_interp_pos")
+    return out
+
+
+_FG_WS: Dict[torch.device, torch.Tensor] = {}
+
+
+def dino_find_fg(labels: torch.Tensor, attn: torch.Tensor, h: int, w: int) -> Dict[str, torch.Tensor]:
+    """`nsos_dino_find_fg` for one image: labels int32 with H*W elements (e.g. [H,W,1]), attn float32 with (H//16)*(W//16)
+    elements -> {'clustering' (labels' shape, int32, oriented), 'attn' [H,W,1] (nearest-upsampled), 'means' float64 [2]
+    (cluster 0, cluster 1), 'flipped' int32 [1]}.  Launches only: no host synchronisation."""
+    for t, name in ((labels, "clustering"), (attn, "attn")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"nerf_sos_amd: `{name}` must be a GPU tensor -- this package has no CPU path")
+    if labels.dtype != torch.int32:
+        raise TypeError(f"find_fg: `clustering` must be int32, got {labels.dtype}")
+    if attn.dtype != torch.float32:
+        raise TypeError(f"find_fg: `attn` must be float32, got {attn.dtype}")
+    if labels.device != attn.device:
+        raise RuntimeError(f"find_fg: `clustering` is on {labels.device}, `attn` on {attn.device}")
+    h, w = int(h), int(w)
+    if h < DINO_PATCH or w < DINO_PATCH or labels.numel() != h * w or attn.numel() != (h // DINO_PATCH) * (w // DINO_PATCH):
+        raise ValueError(f"find_fg: clustering {tuple(labels.shape)} / attn {tuple(attn.shape)} do not fit a {h}x{w} image")
+    labels, attn = labels.contiguous(), attn.contiguous()
+    dev = labels.device
+    if dev not in _FG_WS:
+        _FG_WS[dev] = torch.empty((int(_lib.lib().nsos_dino_find_fg_workspace_bytes()) + 15) // 16 * 4, device=dev, dtype=torch.float32)
+    ws = _FG_WS[dev]
+    out = {"clustering": torch.empty_like(labels), "attn": torch.empty((h, w, 1), device=dev, dtype=torch.float32),
+           "means": torch.empty(2, device=dev, dtype=torch.float64), "flipped": torch.empty(1, device=dev, dtype=torch.int32)}
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nsos_dino_find_fg(_p(labels), _p(attn), h, w, _p(out["clustering"]), _p(out["attn"]), _p(out["means"]),
+                                                _p(out["flipped"]), _p(ws), ws.numel() * 4, _stream()), "nsos_dino_find_fg")
+    return out

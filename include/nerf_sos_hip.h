@@ -788,6 +788,30 @@ int32_t nsos_dino_forward(const float* input, int32_t batch, int32_t in_h, int32
  * (patch_stride <= 0: step 2 alone), exactly the rule the prepare kernel evaluates.  idx: HOST int32 [224]. */
 int32_t nsos_dino_resize_indices(int32_t in_size, int32_t patch_stride, int32_t* idx);
 
+/* ---- DINO ViT-S/16, 16-bit operands (csrc/dino_vit16.hip) ---------------------------------------------------------------------
+ * The same forward pass as nsos_dino_forward (same arguments, flags, outputs -- all fp32 -- and validation) with the two operands of
+ * every matrix product (patch embedding, qkv, q.k^T, p.v, proj, fc1, fc2) in `precision` = NSOS_DTYPE_F16 or NSOS_DTYPE_BF16
+ * (NSOS_DTYPE_F32 is refused with NSOS_ERR_UNSUPPORTED: that is nsos_dino_forward) and fp32 accumulation
+ * (v_mfma_f32_16x16x32_{f16,bf16}).  Each operand is rounded ONCE, to nearest even, by whatever produces it: the weights at pack
+ * time, the im2col tokens, the LayerNorm output, qkv, the probabilities (after the fp32 division), the attention output and the GELU
+ * hidden by their kernels' epilogues.  fp32 throughout: the residual stream, LayerNorm (statistics and affine), softmax (row max,
+ * expf, row sum, division), bias, GELU (erf), the residual add, feat / cls / attn (attn from the fp32 probabilities), `prepared`
+ * (bit-equal to nsos_dino_forward's) and `blocks`.  fp16 has no range check: an operand beyond 65504 becomes infinity; use bf16
+ * for a checkpoint whose activations are not known.
+ * Packed stream (nsos_dino_packed16_bytes() = 43.6 MB, 16-byte aligned): an fp32 section (pos_embed with row 0 = cls_token +
+ * pos_embed[0], every bias and LayerNorm vector), then every weight matrix in 16 bits in nn.Linear's own [out,in] layout (an MFMA
+ * operand fragment is 16 contiguous bytes of a row).  A stream packed for one precision is read only with that precision.
+ * Workspace: nsos_dino_workspace16_bytes(batch) bytes (0 outside 1..NSOS_DINO_MAX_BATCH), 16-byte aligned.
+ * Order (fixed; an image's bits do not depend on the batch): every GEMM output is one fp32 chain over k ascending in steps of 32,
+ * then + bias, GELU, + residual; q.k over d ascending, p.v over the keys ascending (32 at a time); row sums as nsos_dino_forward.
+ * No attribute to configure, no host synchronisation, no allocation: capturable. */
+size_t nsos_dino_packed16_bytes(void);
+int32_t nsos_dino_pack16(const nsos_dino_tensors* tensors, int32_t precision, void* packed, size_t packed_bytes, void* stream);
+size_t nsos_dino_workspace16_bytes(int32_t batch);
+int32_t nsos_dino_forward16(const float* input, int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags,
+                            int32_t precision, const void* packed, void* workspace, size_t workspace_bytes, float* feat, float* cls,
+                            float* attn, float* prepared, float* blocks, void* stream);
+
 /* ---- DINO's full-image path and find_fg (engines/eval.py:133-144 and :237-248) ---------------------------------------------
  * models/extractor.py:215-224 get_vit_attn_feat_noresize: x [B,3,H,W] (or [B,H,W,3] with NSOS_DINO_FULL_NHWC), (x - mean) / std
  * once (twice with NSOS_DINO_FULL_NORMALIZE: eval.py's normalize_batch first), no resize; a rows x cols = (H // 16) x (W // 16)

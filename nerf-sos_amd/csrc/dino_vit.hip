@@ -12,12 +12,11 @@
 // not depend on the batch it travels in.
 #include "common.h"
 #include "mlp_common.h"
+#include "dino_common.h"
 
 namespace {
 
-constexpr int D = NSOS_DINO_WIDTH, T = NSOS_DINO_TOKENS, NP = T - 1, HEADS = NSOS_DINO_HEADS, HD = 64, HID = NSOS_DINO_HIDDEN;
-constexpr int IMG = NSOS_DINO_IMAGE, PS = NSOS_DINO_PATCH, GRID = IMG / PS, KE = 3 * PS * PS;   // 14 patches a side, 768 inputs each
-static_assert(D == HEADS * HD && NP == GRID * GRID, "ViT-S/16 geometry");
+using namespace nsos::dino;   // geometry, resize index rule, prepared pixel, wave reductions: dino_common.h
 
 // ---- packed stream (floats) ----------------------------------------------------------------------------------------------------
 constexpr size_t P_POS = 0;                                  // [197][384], row 0 = cls_token + pos_embed[0]
@@ -36,19 +35,6 @@ constexpr size_t W_X = 0, W_LN = W_X + (size_t)T * D, W_QKV = W_LN + (size_t)T *
                  W_SIZE = W_ROW0 + (size_t)HEADS * NP;
 static_assert(W_SIZE % 4 == 0 && W_LN % 4 == 0 && W_QKV % 4 == 0 && W_TOK % 4 == 0, "16-byte aligned sections for every batch size");
 
-// torch's `nearest` source index (ATen UpSample.h nearest_neighbor_compute_source_index): scale and product in fp32
-__host__ __device__ inline int dino_nearest(int dst, int in, int out) {
-    const float scale = (float)in / (float)out;
-    const int s = (int)floorf((float)dst * scale);
-    return s < in - 1 ? s : in - 1;
-}
-// steps 1-2 composed: 224 -> in*stride -> in  (stride <= 0: 224 -> in)
-__host__ __device__ inline int dino_source_index(int dst, int in, int stride) {
-    if (stride <= 0) return dino_nearest(dst, in, IMG);
-    const int mid = in * stride;
-    return dino_nearest(dino_nearest(dst, mid, IMG), in, mid);
-}
-
 // ---- prepare: tokens[b*196 + t][c*256 + py*16 + px] = prepared[b][c][16*ty + py][16*tx + px]; also x[b][0][:] = cls + pos[0] ----
 __global__ __launch_bounds__(256) void dino_prepare_kernel(const float* __restrict__ in, int batch, int in_h, int in_w, int stride, int flags,
                                                            const float* __restrict__ clspos, float* __restrict__ tokens, float* __restrict__ x,
@@ -61,17 +47,7 @@ __global__ __launch_bounds__(256) void dino_prepare_kernel(const float* __restri
     const int b = (int)(e / ((long long)KE * NP));
     const int c = k >> 8, py = (k >> 4) & 15, px = k & 15;
     const int y = (t / GRID) * PS + py, xx = (t % GRID) * PS + px;
-    float v;
-    if (flags & NSOS_DINO_PREPARED) {
-        v = in[(((size_t)b * 3 + c) * IMG + y) * IMG + xx];
-    } else {
-        const int s1 = (flags & NSOS_DINO_STEP1) ? stride : 0;
-        const int sy = dino_source_index(y, in_h, s1), sx = dino_source_index(xx, in_w, s1);
-        v = (flags & NSOS_DINO_NHWC) ? in[(((size_t)b * in_h + sy) * in_w + sx) * 3 + c] : in[(((size_t)b * 3 + c) * in_h + sy) * in_w + sx];
-        const float mean = c == 0 ? 0.485f : (c == 1 ? 0.456f : 0.406f), sd = c == 0 ? 0.229f : (c == 1 ? 0.224f : 0.225f);
-        if (flags & NSOS_DINO_STEP1) v = (v - mean) / sd;   // engines/trainer.py:24-29 normalize_batch
-        v = (v - mean) / sd;                                // models/extractor.py:205-208
-    }
+    const float v = dino_prepared_pixel(in, b, c, y, xx, in_h, in_w, stride, flags);
     tokens[e] = v;
     if (prepared) prepared[(((size_t)b * 3 + c) * IMG + y) * IMG + xx] = v;
     if (t == 0 && k < D) x[(size_t)b * T * D + k] = clspos[k];
@@ -135,17 +111,6 @@ __global__ __launch_bounds__(256) void dino_gemm_kernel(const float* __restrict_
             out[(size_t)row * N + col] = v;
         }
     }
-}
-
-__device__ __forceinline__ float dino_wave_sum(float v) {   // xor butterfly 32,16,8,4,2,1: every lane ends with the same bits
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ float dino_wave_max(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
 }
 
 // ---- LayerNorm over 384, eps 1e-6 (biased variance about the mean, as nn.LayerNorm); one wave per row ---------------------------
@@ -300,8 +265,6 @@ __global__ __launch_bounds__(256) void dino_add_kernel(const float* __restrict__
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e < n) dst[e] = a[e] + b[e];
 }
-
-inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 
 template <int EPI, int K>
 void launch_gemm(const float* A, const float* Wt, const float* bias, float* out, const float* extra, int M, int N, hipStream_t st, int np = NP) {

@@ -4,6 +4,9 @@ Drop-in for the reference's `VitExtractor` as the trainer uses it (models/extrac
 engines/trainer.py:101-109): the parameters carry the names and shapes of DINO's own checkpoint, so
 `DinoViT().load_state_dict(torch.load("dino_deitsmall16_pretrain.pth"))` takes the file `torch.hub` would have fetched.  Nothing
 here downloads anything.  Forward only (the reference never trains DINO); there is no CPU path.
+
+`DinoViT.precision` chooses the matrix pipe of the 224 x 224 path: "fp32" (default, csrc/dino_vit.hip) or "fp16" / "bf16"
+(csrc/dino_vit16.hip: the operands of every matrix product in 16 bits, fp32 accumulation, everything else fp32).
 """
 from __future__ import annotations
 
@@ -58,10 +61,19 @@ class _PatchEmbed(nn.Module):
 
 class DinoViT(nn.Module):
     """vit_small(patch_size=16) of models/vision_transformer.py, frozen.  150 state-dict tensors under DINO's names; `norm.*` is
-    loaded and never applied (the reference reads block 11's output before the final norm)."""
+    loaded and never applied (the reference reads block 11's output before the final norm).
 
-    def __init__(self):
+    precision: "fp32" (default) | "fp16" | "bf16", a plain attribute like NeRFNet.mlp_precision, checked on assignment; it governs
+    get_vit_attn_feat, patch_features and forward.  The 16-bit settings round the two operands of every matrix product once (weights
+    at pack time, activations in their producer's epilogue) and accumulate in fp32; the residual stream, LayerNorm, softmax, bias,
+    GELU and the outputs stay fp32, and the outputs are fp32 tensors with the same keys and shapes.  fp16 has no range check: an
+    operand beyond 65504 becomes infinity (the largest 16-bit operand of the test weights is 162, tests/golden/
+    dino_vit16.npz), so bf16 -- fp32's range at 8 bits of mantissa, about 8x fp16's error -- is the choice for a checkpoint whose
+    activations are not known.  The full-image path (get_vit_attn_feat_noresize) is fp32 only."""
+
+    def __init__(self, precision: str = "fp32"):
         super().__init__()
+        self.precision = precision
         self.cls_token = nn.Parameter(nn.init.trunc_normal_(torch.empty(1, 1, WIDTH), std=0.02), requires_grad=False)
         self.pos_embed = nn.Parameter(nn.init.trunc_normal_(torch.empty(1, TOKENS, WIDTH), std=0.02), requires_grad=False)
         self.patch_embed = _PatchEmbed()
@@ -69,9 +81,21 @@ class DinoViT(nn.Module):
         self.norm = _Affine((WIDTH,), (WIDTH,), ones=True)
         self._packed = None
         self._packed_key = None
+        self._packed16 = {}          # precision -> (packed stream, key)
         self._workspace = {}
+        self._workspace16 = {}
         self._workspace_full = {}
         self._retired = []
+
+    @property
+    def precision(self) -> str:
+        return self._precision
+
+    @precision.setter
+    def precision(self, value: str):
+        if value not in ops.DINO_PRECISIONS:
+            raise ValueError(f"DinoViT.precision must be one of {list(ops.DINO_PRECISIONS)}, got {value!r}")
+        self._precision = value
 
     # ---- packed weights: once, and again when a parameter's storage or version changed (the pattern of NeRFMLP.packed_weights)
     def _key(self):
@@ -88,8 +112,21 @@ class DinoViT(nn.Module):
             self._packed_key = key
         return self._packed
 
+    def packed_weights16(self, precision: str) -> torch.Tensor:
+        """The 16-bit stream of `precision`, cached next to the fp32 one under the same rule."""
+        key = self._key()
+        packed, have = self._packed16.get(precision, (None, None))
+        if packed is None or key != have or packed.device != self.cls_token.device:
+            if not self.cls_token.is_cuda:
+                raise RuntimeError("nerf_sos_amd: DinoViT must live on a GPU -- this package has no CPU path")
+            reuse = packed if packed is not None and packed.device == self.cls_token.device else None
+            packed = ops.dino_pack16(dict(self.named_parameters()), precision, reuse)
+            self._packed16[precision] = (packed, key)
+        return packed
+
     def invalidate_packed(self):
         self._packed_key = None
+        self._packed16 = {p: (t, None) for p, (t, _) in self._packed16.items()}
 
     def _ws(self, batch: int, device) -> torch.Tensor:
         """ONE workspace per device, grown to the largest batch seen (3.6 MB per image) and reused by every call, so that a
@@ -101,6 +138,16 @@ class DinoViT(nn.Module):
             if ws is not None:
                 self._retired.append(ws)      # a graph captured at the smaller batch still points into it
             ws = self._workspace[key] = ops.dino_workspace(batch, device)
+        return ws
+
+    def _ws16(self, batch: int, device) -> torch.Tensor:
+        """The 16-bit path's workspace (2.0 MB per image), one per device, by the rule of _ws; fp16 and bf16 share it."""
+        key = str(device)
+        ws = self._workspace16.get(key)
+        if ws is None or ws.numel() < ops.dino_workspace16_floats(batch):
+            if ws is not None:
+                self._retired.append(ws)      # a graph captured at the smaller batch still points into it
+            ws = self._workspace16[key] = ops.dino_workspace16(batch, device)
         return ws
 
     def _ws_full(self, batch: int, h: int, w: int, device) -> torch.Tensor:
@@ -116,6 +163,9 @@ class DinoViT(nn.Module):
         return ws
 
     def _run_full(self, x, flags, **want) -> Dict[str, torch.Tensor]:
+        if self.precision != "fp32":
+            raise ValueError(f"DinoViT: the full-image path (get_vit_attn_feat_noresize) is fp32 only -- 16-bit precisions are out "
+                             f"of its scope; set precision = 'fp32' (it is {self.precision!r})")
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise RuntimeError("nerf_sos_amd: DinoViT needs a GPU tensor -- this package has no CPU path")
         if x.dim() != 4:
@@ -128,9 +178,12 @@ class DinoViT(nn.Module):
     def _run(self, x, flags, patch_stride=0, **want) -> Dict[str, torch.Tensor]:
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise RuntimeError("nerf_sos_amd: DinoViT needs a GPU tensor -- this package has no CPU path")
-        packed = self.packed_weights()
+        precision = self.precision
         with torch.no_grad():
-            return ops.dino_forward(x.detach(), packed, flags, patch_stride, self._ws(int(x.shape[0]), x.device), **want)
+            if precision == "fp32":
+                return ops.dino_forward(x.detach(), self.packed_weights(), flags, patch_stride, self._ws(int(x.shape[0]), x.device), **want)
+            return ops.dino_forward16(x.detach(), self.packed_weights16(precision), flags, precision, patch_stride,
+                                      self._ws16(int(x.shape[0]), x.device), **want)
 
     # ---- the reference's interface
     def get_vit_attn_feat(self, x: torch.Tensor, prepared: bool = False, **want) -> Dict[str, torch.Tensor]:

@@ -1165,8 +1165,7 @@ _DINO_BLOCK_FIELDS = (("norm1_w", "norm1.weight"), ("norm1_b", "norm1.bias"), ("
                       ("fc1_w", "mlp.fc1.weight"), ("fc1_b", "mlp.fc1.bias"), ("fc2_w", "mlp.fc2.weight"), ("fc2_b", "mlp.fc2.bias"))
 
 
-def dino_pack(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """DINO's checkpoint tensors (state-dict names, on one GPU) -> the stream nsos_dino_forward reads (`nsos_dino_pack`)."""
+def _dino_pack(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor], precision: str) -> torch.Tensor:
     keep = []
 
     def ptr(name):
@@ -1185,13 +1184,37 @@ def dino_pack(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor] = N
     for i in range(DINO_DEPTH):
         for field, name in _DINO_BLOCK_FIELDS:
             setattr(ts.blocks[i], field, ptr(f"blocks.{i}.{name}"))
-    nbytes = int(_lib.lib().nsos_dino_packed_bytes())
+    nbytes = int(_lib.lib().nsos_dino_packed_bytes() if precision == "fp32" else _lib.lib().nsos_dino_packed16_bytes())
     if packed is None:
         packed = torch.empty((nbytes // 4,), device=keep[0].device, dtype=torch.float32)
     _dino_buffer(packed, "packed", nbytes, keep[0].device)
     with torch.cuda.device(packed.device):
-        _lib.check(_lib.lib().nsos_dino_pack(C.byref(ts), _p(packed), packed.numel() * 4, _stream()), "nsos_dino_pack")
+        if precision == "fp32":
+            _lib.check(_lib.lib().nsos_dino_pack(C.byref(ts), _p(packed), packed.numel() * 4, _stream()), "nsos_dino_pack")
+        else:
+            _lib.check(_lib.lib().nsos_dino_pack16(C.byref(ts), DTYPES[precision], _p(packed), packed.numel() * 4, _stream()),
+                       "nsos_dino_pack16")
     return packed
+
+
+def dino_pack(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """DINO's checkpoint tensors (state-dict names, on one GPU) -> the stream nsos_dino_forward reads (`nsos_dino_pack`)."""
+    return _dino_pack(state, packed, "fp32")
+
+
+DINO_PRECISIONS = ("fp32", "fp16", "bf16")
+
+
+def _dino_precision16(precision: str) -> str:
+    if precision not in ("fp16", "bf16"):
+        raise ValueError(f"dino: the 16-bit entry points take precision 'fp16' or 'bf16', got {precision!r}")
+    return precision
+
+
+def dino_pack16(state: Dict[str, torch.Tensor], precision: str, packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`nsos_dino_pack16`: the stream nsos_dino_forward16 reads at `precision` ("fp16" / "bf16"): an fp32 section (pos_embed, biases,
+    LayerNorm vectors), then every matrix rounded once to 16 bits in its [out,in] layout.  Carried as a float32 tensor (raw bytes)."""
+    return _dino_pack(state, packed, _dino_precision16(precision))
 
 
 def dino_workspace_floats(batch: int) -> int:
@@ -1205,10 +1228,21 @@ def dino_workspace(batch: int, device) -> torch.Tensor:
     return torch.empty((dino_workspace_floats(batch),), device=device, dtype=torch.float32)
 
 
-def dino_forward(x: torch.Tensor, packed: torch.Tensor, flags: int, patch_stride: int = 0, workspace: Optional[torch.Tensor] = None,
-                 want_attn: bool = True, want_prepared: bool = False, want_blocks: bool = False) -> Dict[str, torch.Tensor]:
-    """`nsos_dino_forward`: x [B,h,w,3] (DINO_NHWC) or [B,3,h,w] -> {'feat' [B,196,384], 'cls_' [B,384], 'attn' [B,1,196]}
-    (+ 'prepared' [B,3,224,224], 'blocks' [12,B,197,384] on request).  Launches only; capturable."""
+def dino_workspace16_floats(batch: int) -> int:
+    """The 16-bit path's workspace (`nsos_dino_workspace16_bytes`) as a count of float32 elements (the buffer is raw bytes)."""
+    nbytes = int(_lib.lib().nsos_dino_workspace16_bytes(int(batch)))
+    if nbytes == 0:
+        raise ValueError(f"dino: batch size {batch} outside what the kernels take")
+    return nbytes // 4
+
+
+def dino_workspace16(batch: int, device) -> torch.Tensor:
+    return torch.empty((dino_workspace16_floats(batch),), device=device, dtype=torch.float32)
+
+
+def _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, precision) -> Dict[str, torch.Tensor]:
+    L = _lib.lib()
+    f32 = precision == "fp32"
     x = _dev(x, "x")
     if x.dim() != 4:
         raise ValueError(f"dino: expected a 4-d image batch, got {tuple(x.shape)}")
@@ -1218,9 +1252,9 @@ def dino_forward(x: torch.Tensor, packed: torch.Tensor, flags: int, patch_stride
         raise ValueError(f"dino: expected 3 channels, got {tuple(x.shape)}")
     dev = x.device
     if workspace is None:
-        workspace = dino_workspace(B, dev)
-    _dino_buffer(packed, "packed", int(_lib.lib().nsos_dino_packed_bytes()), dev)
-    nws = int(_lib.lib().nsos_dino_workspace_bytes(B))
+        workspace = dino_workspace(B, dev) if f32 else dino_workspace16(B, dev)
+    _dino_buffer(packed, "packed", int(L.nsos_dino_packed_bytes() if f32 else L.nsos_dino_packed16_bytes()), dev)
+    nws = int(L.nsos_dino_workspace_bytes(B) if f32 else L.nsos_dino_workspace16_bytes(B))
     if nws == 0:
         raise ValueError(f"dino: batch size {B} outside what the kernels take")
     _dino_buffer(workspace, "workspace", nws, dev)
@@ -1232,11 +1266,31 @@ def dino_forward(x: torch.Tensor, packed: torch.Tensor, flags: int, patch_stride
         out["prepared"] = torch.empty((B, 3, DINO_IMAGE, DINO_IMAGE), device=dev, dtype=torch.float32)
     if want_blocks:
         out["blocks"] = torch.empty((DINO_DEPTH, B, DINO_TOKENS, DINO_WIDTH), device=dev, dtype=torch.float32)
+    outs = (_p(out["feat"]), _p(out["cls_"]), _p(out.get("attn")), _p(out.get("prepared")), _p(out.get("blocks")), _stream())
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nsos_dino_forward(_p(x), B, h, w, int(patch_stride), int(flags), _p(packed), _p(workspace), workspace.numel() * 4,
-                                                _p(out["feat"]), _p(out["cls_"]), _p(out.get("attn")), _p(out.get("prepared")),
-                                                _p(out.get("blocks")), _stream()), "nsos_dino_forward")
+        if f32:
+            _lib.check(L.nsos_dino_forward(_p(x), B, h, w, int(patch_stride), int(flags), _p(packed), _p(workspace), workspace.numel() * 4,
+                                           *outs), "nsos_dino_forward")
+        else:
+            _lib.check(L.nsos_dino_forward16(_p(x), B, h, w, int(patch_stride), int(flags), DTYPES[precision], _p(packed), _p(workspace),
+                                             workspace.numel() * 4, *outs), "nsos_dino_forward16")
     return out
+
+
+def dino_forward(x: torch.Tensor, packed: torch.Tensor, flags: int, patch_stride: int = 0, workspace: Optional[torch.Tensor] = None,
+                 want_attn: bool = True, want_prepared: bool = False, want_blocks: bool = False) -> Dict[str, torch.Tensor]:
+    """`nsos_dino_forward`: x [B,h,w,3] (DINO_NHWC) or [B,3,h,w] -> {'feat' [B,196,384], 'cls_' [B,384], 'attn' [B,1,196]}
+    (+ 'prepared' [B,3,224,224], 'blocks' [12,B,197,384] on request).  Launches only; capturable."""
+    return _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, "fp32")
+
+
+def dino_forward16(x: torch.Tensor, packed: torch.Tensor, flags: int, precision: str, patch_stride: int = 0,
+                   workspace: Optional[torch.Tensor] = None, want_attn: bool = True, want_prepared: bool = False,
+                   want_blocks: bool = False) -> Dict[str, torch.Tensor]:
+    """`nsos_dino_forward16`: dino_forward with the operands of every matrix product in `precision` ("fp16" / "bf16") and fp32
+    accumulation; `packed` from dino_pack16 at the same precision, `workspace` from dino_workspace16.  Outputs are fp32 tensors of the
+    same keys and shapes.  Launches only; capturable."""
+    return _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, _dino_precision16(precision))
 
 
 def dino_resize_indices(in_size: int, patch_stride: int = 0):

@@ -31,7 +31,9 @@ extern "C" {
  * sem_hid16 of the default 16-bit kernel, nsos_mlp_save16_layout's NSOS_SEM_HID_TILED bit; 6: `scale` of nsos_mlp_input_grads_x3[_a16]
  * is three floats -- trunk scale, colour-branch factor, semantic-branch factor; 7: the generic kernels' packed program gained a field
  * (GenOp::ksplit_off: an older binding's buffer sizes still agree, but the two sides must match) + nsos_wgrad_batch; 9: evaluation metrics
- * nsos_ssim, nsos_adjusted_rand, nsos_kmeans; 10: the DINO ViT-S/16 feature extractor nsos_dino_*) */
+ * nsos_ssim, nsos_adjusted_rand, nsos_kmeans; 10: the DINO ViT-S/16 feature extractor nsos_dino_*).  The folded fp32 stream
+ * (nsos_mlp_pack_fold / nsos_mlp_*_fold) only ADDS entry points -- no existing argument list or buffer format moved, so the version
+ * stands; a library without them fails to bind (every declared symbol is resolved at load) and reports another source hash. */
 #define NSOS_ABI_VERSION 10
 
 enum {
@@ -90,6 +92,20 @@ const char* nsos_error_string(int32_t code);
 size_t nsos_mlp_packed_bytes(int32_t sem_mode);
 int32_t nsos_mlp_pack(const nsos_mlp_tensors* tensors, int32_t sem_mode, void* packed, size_t packed_bytes,
                       void* stream);
+/* The FOLDED stream.  feature_linear has no activation behind it (models/nerf_mlp.py:86-90) and its only consumer is
+ * views_linears.0, so W' = W_v[:, :256] W_f [128,256] and b' = W_v[:, :256] b_f + b_v depend on the weights alone, and
+ *   relu(views_linears.0(cat([feature_linear(h7), d27]))) = relu(W' h7 + W_v[:, 256:] d27 + b').
+ * nsos_mlp_pack_fold forms W' and b' on the device (one small kernel in front of the pack kernel, stream-ordered, no allocation,
+ * no host synchronisation: capturable) -- fp64 accumulation in the fixed order j = 0..255, separate multiply and add, ONE
+ * rounding to fp32 -- into a scratch region at the end of `packed` (float offset nsos_mlp_packed_bytes(sem_mode) / 4:
+ * [W' | W_v[:, 256:]] as [128,283] row-major, then b' [128]) and packs the view layer from there; the eight feature_linear
+ * chunks move to the END of the stream, where only the full-backward variant (which stores the feature vector) reads them.
+ * `packed` holds nsos_mlp_packed_bytes_fold(sem_mode) bytes and is consumed ONLY by the nsos_mlp_*_fold entries below, which
+ * take the arguments of their namesakes.  sigma, the semantic logits and every saved block except NSOS_ACTS_VIEWS are
+ * bit-identical to the unfolded kernels'; rgb differs by rounding (one 256-term chain instead of two), 11 % fewer MFMAs. */
+size_t nsos_mlp_packed_bytes_fold(int32_t sem_mode);
+int32_t nsos_mlp_pack_fold(const nsos_mlp_tensors* tensors, int32_t sem_mode, void* packed, size_t packed_bytes,
+                           void* stream);
 
 /* ---- K2-G: the MLP for any architecture the reference's constructors accept (csrc/mlp_generic.hip) -------------------------
  * nn.Linear tensors ([out,in] row-major fp32, device memory) of ONE NeRFMLP.mlp, described as the reference builds it
@@ -270,6 +286,12 @@ int32_t nsos_mlp_forward_rays(const void* packed, int32_t sem_mode, const float*
  * export (engines/eval.py:297; models/nerf_mlp.py:179-215).  pts, dirs [P,3]; raw out [P,C]. */
 int32_t nsos_mlp_forward_points(const void* packed, int32_t sem_mode, const float* pts, const float* dirs,
                                 int64_t n_pts, float* raw, void* stream);
+/* The same two on the folded stream of nsos_mlp_pack_fold. */
+int32_t nsos_mlp_forward_rays_fold(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
+                                   const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples,
+                                   float* raw, void* stream);
+int32_t nsos_mlp_forward_points_fold(const void* packed, int32_t sem_mode, const float* pts, const float* dirs,
+                                     int64_t n_pts, float* raw, void* stream);
 
 /* ---- K5: training with a frozen backbone (run_nerf.py:307-318, --fix_backbone) -------------------------------
  * nsos_mlp_forward_rays_save = nsos_mlp_forward_rays that also stores, per point, what the semantic head's
@@ -283,6 +305,9 @@ int32_t nsos_mlp_forward_points(const void* packed, int32_t sem_mode, const floa
 int32_t nsos_mlp_forward_rays_save(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
                                    const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples,
                                    float* raw, float* sem_in, float* sem_hid, void* stream);
+int32_t nsos_mlp_forward_rays_save_fold(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
+                                        const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples,
+                                        float* raw, float* sem_in, float* sem_hid, void* stream);   /* folded stream; raw = nsos_mlp_forward_rays_fold's */
 /* ---- K7: full backward (every parameter trainable) --------------------------------------------------
  * nsos_mlp_forward_rays_save_all = nsos_mlp_forward_rays that also stores every layer's activations, row-major
  * acts out [R*S, NSOS_ACTS_DIM] fp32, so that the backward is GEMMs + masks over saved data:
@@ -299,6 +324,11 @@ int32_t nsos_mlp_forward_rays_save(const void* packed, int32_t sem_mode, const f
 int32_t nsos_mlp_forward_rays_save_all(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
                                        const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples,
                                        float* raw, float* acts, void* stream);
+/* On the folded stream: raw bit-identical to nsos_mlp_forward_rays_fold; NSOS_ACTS_VIEWS comes from the folded chain,
+ * NSOS_ACTS_FEAT is feature_linear(h7) as before (computed for storing only: it is an operand of views_linears.0's weight gradient). */
+int32_t nsos_mlp_forward_rays_save_all_fold(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
+                                            const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples,
+                                            float* raw, float* acts, void* stream);
 /* Building blocks of the full backward over saved activations (the input-gradient GEMMs g_in = g_out W are plain
  * [P,256]x[256,256] products and go through the BLAS library):
  * nsos_wgrad: dW [M, N] (row stride ldw) = sum_p G[p, 0:M]^T X[p, 0:N], db [M] = sum_p G[p, 0:M] (db may be NULL);
@@ -474,6 +504,10 @@ int32_t nsos_mlp_input_grads_x3(const void* packed, int32_t sem_mode, const floa
 int32_t nsos_mlp_profile_rays(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
                               const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples,
                               float* raw, uint64_t* stamps, void* stream);
+/* ... of the folded kernel (slot 10, the feature_linear phase, is empty: stamped together with slot 9's end). */
+int32_t nsos_mlp_profile_rays_fold(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
+                                   const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples,
+                                   float* raw, uint64_t* stamps, void* stream);
 /* Same for the reduced-precision kernel; it stamps the SECOND tile of workgroups 0..3 (steady state), so give it
  * more than 2 x 256 x (CU count) points.  Slot meaning: scripts/phase_profile_lp.py. */
 /* Diagnostics: stamp EVERY following 16-bit MLP launch (the training variants included) into `stamps` (layout of

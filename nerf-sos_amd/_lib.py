@@ -63,6 +63,8 @@ SIGNATURES = {
     "nsos_source_hash": (C.c_char_p, []),
     "nsos_mlp_packed_bytes": (_sz, [_i32]),
     "nsos_mlp_pack": (_i32, [C.POINTER(MlpTensors), _i32, _fp, _sz, _fp]),
+    "nsos_mlp_packed_bytes_fold": (_sz, [_i32]),
+    "nsos_mlp_pack_fold": (_i32, [C.POINTER(MlpTensors), _i32, _fp, _sz, _fp]),
     "nsos_mlp_generic_packed_bytes": (_sz, [C.POINTER(GenericMlp)]),
     "nsos_mlp_generic_out_channels": (_i32, [C.POINTER(GenericMlp)]),
     "nsos_mlp_generic_pack": (_i32, [C.POINTER(GenericMlp), _fp, _sz, _fp]),
@@ -93,6 +95,9 @@ SIGNATURES = {
     "nsos_mlp_forward_rays": (_i32, [_fp, _i32, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _fp]),
     "nsos_mlp_forward_rays_save": (_i32, [_fp, _i32, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _fp, _fp, _fp]),
     "nsos_mlp_forward_rays_save_all": (_i32, [_fp, _i32, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _fp, _fp]),
+    "nsos_mlp_forward_rays_fold": (_i32, [_fp, _i32, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _fp]),
+    "nsos_mlp_forward_rays_save_fold": (_i32, [_fp, _i32, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _fp, _fp, _fp]),
+    "nsos_mlp_forward_rays_save_all_fold": (_i32, [_fp, _i32, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _fp, _fp]),
     "nsos_wgrad_workspace_bytes": (_sz, []),
     "nsos_wgrad": (_i32, [_fp, _i32, _fp, _i32, _i64, _i32, _i32, _fp, _i32, _fp, _fp, _sz, _fp]),
     "nsos_wgrad_x3": (_i32, [_fp, _i32, _fp, _i32, _i64, _fp, _i32, _fp, _fp, _sz, _fp]),
@@ -112,6 +117,7 @@ SIGNATURES = {
     "nsos_mlp_forward_rays_save16_lp": (_i32, [_fp, _i32, _i32, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _fp, _fp, _fp]),
     "nsos_mlp_save16_layout": (_i32, [_i64]),
     "nsos_mlp_profile_rays": (_i32, [_fp, _i32, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _fp, _fp]),
+    "nsos_mlp_profile_rays_fold": (_i32, [_fp, _i32, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _fp, _fp]),
     "nsos_mlp_packed_bytes_x3": (_sz, [_i32]),
     "nsos_mlp_pack_x3": (_i32, [C.POINTER(MlpTensors), _i32, _fp, _sz, _fp]),
     "nsos_mlp_forward_rays_x3": (_i32, [_fp, _i32, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _fp]),
@@ -131,6 +137,7 @@ SIGNATURES = {
     "nsos_mlp_lp_set_stamp_buffer": (_i32, [_fp]),
     "nsos_mlp_profile_rays_lp": (_i32, [_fp, _i32, _i32, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _fp, _fp]),
     "nsos_mlp_forward_points": (_i32, [_fp, _i32, _fp, _fp, _i64, _fp, _fp]),
+    "nsos_mlp_forward_points_fold": (_i32, [_fp, _i32, _fp, _fp, _i64, _fp, _fp]),
     "nsos_composite": (_i32, [_fp, _fp, _fp, _fp, _f32, _i64, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "nsos_composite_importance": (_i32, [_fp, _fp, _fp, _fp, _f32, _i64, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32,
                                          _fp, _fp, _fp, _fp]),

@@ -54,10 +54,21 @@ constexpr int kAuxFloats = 1024;
 // order; Enc = the 63 encoded-xyz features (+1 pad) in natural order; Dir = the 27 encoded-direction features.
 enum SegKind { kHid8 = 0, kEnc8 = 1, kHid4 = 2, kEnc4 = 3, kDir4 = 4 };
 
-__host__ __device__ constexpr int chunks_per_net(int sem) {
+__host__ __device__ constexpr int chunks_per_net(int sem, bool with_feature = true) {
     // L0 enc(2) + L1-4 (4x8) + L5 hid(8)+enc(2) + L6,L7 (2x8) + [sem0 hid(4) (+enc 1)] + feature(8) + views hid(4)+dir(1)
-    return 2 + 32 + 10 + 16 + (sem ? 4 + (sem == 2 ? 1 : 0) : 0) + 8 + 5;
+    // with_feature = false: what the folded eval / SAVE 1 kernels consume (feature_linear folded into the view layer)
+    return 2 + 32 + 10 + 16 + (sem ? 4 + (sem == 2 ? 1 : 0) : 0) + (with_feature ? 8 : 0) + 5;
 }
+
+// Folded stream (nsos_mlp_pack_fold): feature_linear has no activation behind it and views_linears.0 is its only consumer, so
+//   W' = W_v[:, :256] W_f   (128 x 256),   b' = W_v[:, :256] b_f + b_v,   v = relu(W' h7 + W_v[:, 256:] d27 + b')
+// depend on the weights alone.  fold_kernel writes [W' | W_v[:, 256:]] as one [128, 283] matrix (the layout of
+// views_linears.0.weight) and b' into a scratch region behind the chunks of the SAME packed buffer; pack_kernel then takes the
+// view segment from there.  Chunk order of the folded stream: ... L7, [sem0], views hid(4)+dir(1), feature(8) LAST: the eval and
+// SAVE 1 kernels wrap their cyclic DMA in front of the feature chunks, SAVE 2 (which must store the feature vector, an operand
+// of dW_views) runs through them after the rgb head.
+constexpr int kFoldViewsFloats = 128 * (NSOS_NET_WIDTH + NSOS_DIR_DIM);  // [128, 283]
+constexpr int kFoldScratchFloats = kFoldViewsFloats + 128;               // + b'
 
 constexpr int kProfSlots = 64;
 struct MlpParams {
@@ -184,12 +195,13 @@ __device__ __forceinline__ void enc_fill(f32x16& out, const Enc<L, ParityHalf>& 
 // ------------------------------------------------------------------------------------------ the kernel
 // SAVE: training-mode variants that additionally store what a backward pass needs --
 //   1: the semantic head's operands only (frozen backbone, K5);  2: every layer's activations (full backward, K7).
-template <int SEM, bool RAYS, int SAVE = 0>
+// FOLD: the folded stream (see chunks_per_net): the layer loop ends at h7 and the view branch contracts relu(h7) against W'.
+template <int SEM, bool RAYS, int SAVE = 0, bool FOLD = false>
 __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const MlpParams P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];  // 3 x 36 KiB weight slots
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pj = lane & 31, hi = lane >> 5;
-    constexpr int NCH = chunks_per_net(SEM);
+    constexpr int NCH = chunks_per_net(SEM, !FOLD || SAVE == 2);  // chunks consumed per tile = period of the cyclic DMA
     constexpr int C = SEM ? 6 : 4;
 
     // ---- weight stream (see "A-operand pipeline" above).  State, all advanced by register rotation in tail():
@@ -324,9 +336,9 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const MlpParams P) {
         activate(H, Z, relu);
         if constexpr (SAVE == 2) save_layer(0);
         stamp();  // 2
-        // pts_linears.1..7 (l = 1..7) and feature_linear (l = 8): Z = bias + W * H
+        // pts_linears.1..7 (l = 1..7) and feature_linear (l = 8; not FOLD): Z = bias + W * H
 #pragma unroll 1
-        for (int l = 1; l <= 8; ++l) {
+        for (int l = 1; l <= (FOLD ? 7 : 8); ++l) {
             static_for<0, 8>([&](auto cc) {
                 constexpr int c = decltype(cc)::value;
                 chunk8<(c == 0)>(Z, ring, stage_begin(), H[c], side, mid, tail);
@@ -389,7 +401,8 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const MlpParams P) {
                 }
             }
         }
-        // ---- view branch (models/nerf_mlp.py:87-92): cat([feature, dir27]) -> 128 -> rgb.  H = feature.
+        if constexpr (FOLD) stamp();  // 10: keeps the later stamps' slots (no feature_linear phase here)
+        // ---- view branch (models/nerf_mlp.py:87-92): cat([feature, dir27]) -> 128 -> rgb.  H = feature (FOLD: relu(h7), against W').
         f32x16 vacc[4];
         static_for<0, 4>([&](auto cc) {
             constexpr int c = decltype(cc)::value;
@@ -416,6 +429,16 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const MlpParams P) {
             rgb[o] = both_halves(pr);
         }
         stamp();  // 11: view branch + rgb head done
+        if constexpr (FOLD && SAVE == 2) {
+            // the feature vector is an operand of dW_views: feature_linear runs for storing only, after the view branch has
+            // consumed H = relu(h7) (these eight chunks are the last of the folded stream)
+            static_for<0, 8>([&](auto cc) {
+                constexpr int c = decltype(cc)::value;
+                chunk8<(c == 0)>(Z, ring, stage_begin(), H[c], side, mid, tail);
+            });
+            activate(H, Z, pass);
+            save_layer(256 * 8);
+        }
         // ---- raw = [r, g, b, sigma, (sem0, sem1)]   (models/nerf_mlp.py:93-96)
         if (poison != poison) {
             const float qnan = __builtin_nanf("");
@@ -463,6 +486,40 @@ struct PackParams {
     float* aux;
     float* chunks;
 };
+
+// W' and b' of the folded stream (see chunks_per_net).  One thread per element of [128, 283] (+ 128 for b'); consecutive
+// threads walk a row of W', so feature_w[j][k] is read coalesced and views_w[i][j] is a broadcast.  fp64 accumulation in the
+// fixed order j = 0..255 with a separate multiply and add (the file is compiled with -ffp-contract=off), rounded ONCE to fp32.
+__global__ __launch_bounds__(256) void fold_kernel(const float* __restrict__ views_w, const float* __restrict__ views_b,
+                                                   const float* __restrict__ feature_w, const float* __restrict__ feature_b,
+                                                   float* __restrict__ scratch) {
+    constexpr int W = NSOS_NET_WIDTH, IN = NSOS_NET_WIDTH + NSOS_DIR_DIM;
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= kFoldScratchFloats) return;
+    if (gid >= kFoldViewsFloats) {  // b'[i] = (sum_j W_v[i][j] b_f[j]) + b_v[i]
+        const int i = gid - kFoldViewsFloats;
+        double acc = 0.0;
+        for (int j = 0; j < W; ++j) {
+            const double prod = (double)views_w[i * IN + j] * (double)feature_b[j];
+            acc = acc + prod;
+        }
+        acc = acc + (double)views_b[i];
+        scratch[gid] = (float)acc;
+        return;
+    }
+    const int i = gid / IN, k = gid - i * IN;
+    if (k >= W) {  // the direction columns travel unchanged
+        scratch[gid] = views_w[gid];
+        return;
+    }
+    double acc = 0.0;
+#pragma unroll 8
+    for (int j = 0; j < W; ++j) {
+        const double prod = (double)views_w[i * IN + j] * (double)feature_w[j * W + k];
+        acc = acc + prod;
+    }
+    scratch[gid] = (float)acc;
+}
 
 __global__ __launch_bounds__(256) void pack_kernel(const PackParams P) {
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -519,27 +576,29 @@ int num_cus() { return nsos_device_cus(); }
 
 constexpr int kLdsBytes = 3 * kSlotFloats * 4;
 
-template <int SEM, bool RAYS, int SAVE = 0>
+template <int SEM, bool RAYS, int SAVE = 0, bool FOLD = false>
 int32_t launch_mlp(const MlpParams& p, hipStream_t stream) {
     static NsosPerDeviceFlag configured_on;
     bool& configured = configured_on.here();
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<SEM, RAYS, SAVE>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<SEM, RAYS, SAVE, FOLD>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
         if (e != hipSuccess) return (int32_t)e;
         configured = true;
     }
     const int grid = p.n_tiles < num_cus() ? p.n_tiles : num_cus();
-    hipLaunchKernelGGL((mlp_fused_kernel<SEM, RAYS, SAVE>), dim3(grid), dim3(256), kLdsBytes, stream, p);
+    hipLaunchKernelGGL((mlp_fused_kernel<SEM, RAYS, SAVE, FOLD>), dim3(grid), dim3(256), kLdsBytes, stream, p);
     return nsos_launch_status();
 }
 
-template <bool RAYS>
+template <bool RAYS, int SAVE = 0, bool FOLD = false>
 int32_t dispatch_mlp(int sem_mode, const MlpParams& p, hipStream_t stream) {
     switch (sem_mode) {
-        case NSOS_SEM_NONE: return launch_mlp<0, RAYS>(p, stream);
-        case NSOS_SEM_PLAIN: return launch_mlp<1, RAYS>(p, stream);
-        case NSOS_SEM_COORD: return launch_mlp<2, RAYS>(p, stream);
+        case NSOS_SEM_NONE:
+            if constexpr (SAVE != 1) return launch_mlp<0, RAYS, SAVE, FOLD>(p, stream);
+            break;
+        case NSOS_SEM_PLAIN: return launch_mlp<1, RAYS, SAVE, FOLD>(p, stream);
+        case NSOS_SEM_COORD: return launch_mlp<2, RAYS, SAVE, FOLD>(p, stream);
     }
     return NSOS_ERR_UNSUPPORTED;
 }
@@ -560,19 +619,14 @@ int32_t fill_ray_params(MlpParams& p, const void* packed, const float* rays_o, c
     return NSOS_OK;
 }
 
-}  // namespace
-
-// ------------------------------------------------------------------------------------------ C ABI
-extern "C" size_t nsos_mlp_packed_bytes(int32_t sem_mode) {
-    if (sem_mode < 0 || sem_mode > 2) return 0;
-    return sizeof(float) * ((size_t)kAuxFloats + (size_t)chunks_per_net(sem_mode) * kSlotFloats);
+size_t packed_floats(int sem_mode, bool fold) {
+    return (size_t)kAuxFloats + (size_t)chunks_per_net(sem_mode) * kSlotFloats + (fold ? (size_t)kFoldScratchFloats : 0);
 }
 
-extern "C" int32_t nsos_mlp_pack(const nsos_mlp_tensors* T, int32_t sem_mode, void* packed, size_t packed_bytes,
-                                 void* stream) {
+int32_t pack_impl(const nsos_mlp_tensors* T, int32_t sem_mode, void* packed, size_t packed_bytes, void* stream, bool fold) {
     NSOS_REQUIRE(T && packed, NSOS_ERR_NULL_POINTER);
     NSOS_REQUIRE(sem_mode >= 0 && sem_mode <= 2, NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(packed_bytes >= nsos_mlp_packed_bytes(sem_mode), NSOS_ERR_BUFFER_TOO_SMALL);
+    NSOS_REQUIRE(packed_bytes >= sizeof(float) * packed_floats(sem_mode, fold), NSOS_ERR_BUFFER_TOO_SMALL);
     NSOS_REQUIRE(((uintptr_t)packed & 15) == 0, NSOS_ERR_MISALIGNED);
     for (int l = 0; l < NSOS_NET_DEPTH; ++l) NSOS_REQUIRE(T->pts_w[l] && T->pts_b[l], NSOS_ERR_NULL_POINTER);
     NSOS_REQUIRE(T->alpha_w && T->alpha_b && T->feature_w && T->feature_b && T->views_w && T->views_b &&
@@ -597,36 +651,50 @@ extern "C" int32_t nsos_mlp_pack(const nsos_mlp_tensors* T, int32_t sem_mode, vo
         add(T->sem0_w, T->sem0_b, in_dim, 0, kHid4, 4);
         if (sem_mode == NSOS_SEM_COORD) add(T->sem0_w, nullptr, in_dim, W, kEnc4, 1);
     }
-    add(T->feature_w, T->feature_b, W, 0, kHid8, 8);
-    add(T->views_w, T->views_b, W + NSOS_DIR_DIM, 0, kHid4, 4);  // cat([feature, dir27]) (models/nerf_mlp.py:87)
-    add(T->views_w, nullptr, W + NSOS_DIR_DIM, W, kDir4, 1);
+    float* const aux = static_cast<float*>(packed);
+    if (!fold) {
+        add(T->feature_w, T->feature_b, W, 0, kHid8, 8);
+        add(T->views_w, T->views_b, W + NSOS_DIR_DIM, 0, kHid4, 4);  // cat([feature, dir27]) (models/nerf_mlp.py:87)
+        add(T->views_w, nullptr, W + NSOS_DIR_DIM, W, kDir4, 1);
+    } else {  // the view layer from the folded matrix [W' | W_v[:, 256:]] and b' (fold_kernel, same stream); feature_linear last
+        float* const scratch = aux + kAuxFloats + (size_t)chunks_per_net(sem_mode) * kSlotFloats;
+        hipLaunchKernelGGL(fold_kernel, dim3((kFoldScratchFloats + 255) / 256), dim3(256), 0, (hipStream_t)stream, T->views_w,
+                           T->views_b, T->feature_w, T->feature_b, scratch);
+        const int32_t rc = nsos_launch_status();
+        if (rc != NSOS_OK) return rc;
+        add(scratch, scratch + kFoldViewsFloats, W + NSOS_DIR_DIM, 0, kHid4, 4);
+        add(scratch, nullptr, W + NSOS_DIR_DIM, W, kDir4, 1);
+        add(T->feature_w, T->feature_b, W, 0, kHid8, 8);
+    }
     P.n_seg = n;
     P.n_chunks = chunks_per_net(sem_mode);
     P.alpha_w = T->alpha_w; P.alpha_b = T->alpha_b;
     P.rgb_w = T->rgb_w; P.rgb_b = T->rgb_b;
     P.sem2_w = sem_mode ? T->sem2_w : nullptr;
     P.sem2_b = sem_mode ? T->sem2_b : nullptr;
-    P.aux = static_cast<float*>(packed);
+    P.aux = aux;
     P.chunks = P.aux + kAuxFloats;
     const long long total = (long long)P.n_chunks * kSlotFloats;
     hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P);
     return nsos_launch_status();
 }
 
-extern "C" int32_t nsos_mlp_forward_rays(const void* packed, int32_t sem_mode, const float* rays_o,
-                                         const float* rays_d, const float* viewdirs, const float* z_vals,
-                                         int64_t n_rays, int32_t n_samples, float* raw, void* stream) {
+// The entry points' bodies; FOLD: the folded stream of nsos_mlp_pack_fold and the kernels that consume it.
+template <bool FOLD>
+int32_t forward_rays(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d, const float* viewdirs,
+                     const float* z_vals, int64_t n_rays, int32_t n_samples, float* raw, uint64_t* stamps, void* stream) {
     if (n_rays == 0) return NSOS_OK;  // empty batch: nothing to launch (empty tensors have NULL data pointers)
     MlpParams p;
     const int32_t rc = fill_ray_params(p, packed, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw);
     if (rc != NSOS_OK) return rc;
-    return dispatch_mlp<true>(sem_mode, p, (hipStream_t)stream);
+    p.prof = reinterpret_cast<unsigned long long*>(stamps);  // diagnostics (nsos_mlp_profile_rays[_fold]), else NULL
+    return dispatch_mlp<true, 0, FOLD>(sem_mode, p, (hipStream_t)stream);
 }
 
-extern "C" int32_t nsos_mlp_forward_rays_save(const void* packed, int32_t sem_mode, const float* rays_o,
-                                              const float* rays_d, const float* viewdirs, const float* z_vals,
-                                              int64_t n_rays, int32_t n_samples, float* raw, float* sem_in,
-                                              float* sem_hid, void* stream) {
+template <bool FOLD>
+int32_t forward_rays_save(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
+                          const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples, float* raw,
+                          float* sem_in, float* sem_hid, void* stream) {
     if (n_rays == 0) return NSOS_OK;
     NSOS_REQUIRE(sem_in && sem_hid, NSOS_ERR_NULL_POINTER);
     NSOS_REQUIRE(sem_mode == NSOS_SEM_PLAIN || sem_mode == NSOS_SEM_COORD, NSOS_ERR_UNSUPPORTED);
@@ -636,13 +704,13 @@ extern "C" int32_t nsos_mlp_forward_rays_save(const void* packed, int32_t sem_mo
     if (rc != NSOS_OK) return rc;
     p.sem_in = sem_in;
     p.sem_hid = sem_hid;
-    return sem_mode == NSOS_SEM_COORD ? launch_mlp<2, true, true>(p, (hipStream_t)stream)
-                                      : launch_mlp<1, true, true>(p, (hipStream_t)stream);
+    return dispatch_mlp<true, 1, FOLD>(sem_mode, p, (hipStream_t)stream);
 }
 
-extern "C" int32_t nsos_mlp_forward_rays_save_all(const void* packed, int32_t sem_mode, const float* rays_o,
-                                                  const float* rays_d, const float* viewdirs, const float* z_vals,
-                                                  int64_t n_rays, int32_t n_samples, float* raw, float* acts, void* stream) {
+template <bool FOLD>
+int32_t forward_rays_save_all(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
+                              const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples, float* raw,
+                              float* acts, void* stream) {
     if (n_rays == 0) return NSOS_OK;
     NSOS_REQUIRE(acts, NSOS_ERR_NULL_POINTER);
     NSOS_REQUIRE(((uintptr_t)acts & 15) == 0, NSOS_ERR_MISALIGNED);
@@ -650,29 +718,12 @@ extern "C" int32_t nsos_mlp_forward_rays_save_all(const void* packed, int32_t se
     const int32_t rc = fill_ray_params(p, packed, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw);
     if (rc != NSOS_OK) return rc;
     p.acts = acts;
-    switch (sem_mode) {
-        case NSOS_SEM_NONE: return launch_mlp<0, true, 2>(p, (hipStream_t)stream);
-        case NSOS_SEM_PLAIN: return launch_mlp<1, true, 2>(p, (hipStream_t)stream);
-        case NSOS_SEM_COORD: return launch_mlp<2, true, 2>(p, (hipStream_t)stream);
-    }
-    return NSOS_ERR_UNSUPPORTED;
+    return dispatch_mlp<true, 2, FOLD>(sem_mode, p, (hipStream_t)stream);
 }
 
-extern "C" int32_t nsos_mlp_profile_rays(const void* packed, int32_t sem_mode, const float* rays_o,
-                                         const float* rays_d, const float* viewdirs, const float* z_vals,
-                                         int64_t n_rays, int32_t n_samples, float* raw, uint64_t* stamps,
-                                         void* stream) {
-    if (n_rays == 0) return NSOS_OK;
-    NSOS_REQUIRE(stamps, NSOS_ERR_NULL_POINTER);
-    MlpParams p;
-    const int32_t rc = fill_ray_params(p, packed, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw);
-    if (rc != NSOS_OK) return rc;
-    p.prof = reinterpret_cast<unsigned long long*>(stamps);
-    return dispatch_mlp<true>(sem_mode, p, (hipStream_t)stream);
-}
-
-extern "C" int32_t nsos_mlp_forward_points(const void* packed, int32_t sem_mode, const float* pts,
-                                           const float* dirs, int64_t n_pts, float* raw, void* stream) {
+template <bool FOLD>
+int32_t forward_points(const void* packed, int32_t sem_mode, const float* pts, const float* dirs, int64_t n_pts, float* raw,
+                       void* stream) {
     if (n_pts == 0) return NSOS_OK;  // empty batch: nothing to launch (empty tensors have NULL data pointers)
     NSOS_REQUIRE(packed && pts && dirs && raw, NSOS_ERR_NULL_POINTER);
     NSOS_REQUIRE(n_pts >= 0, NSOS_ERR_BAD_SHAPE);
@@ -683,5 +734,67 @@ extern "C" int32_t nsos_mlp_forward_points(const void* packed, int32_t sem_mode,
     p.chunks = p.aux + kAuxFloats;
     p.pts = pts; p.dirs = dirs; p.raw = raw; p.n_pts = n_pts; p.n_samples = 1;
     p.n_tiles = (int)((n_pts + kTilePts - 1) / kTilePts);
-    return dispatch_mlp<false>(sem_mode, p, (hipStream_t)stream);
+    return dispatch_mlp<false, 0, FOLD>(sem_mode, p, (hipStream_t)stream);
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------ C ABI
+extern "C" size_t nsos_mlp_packed_bytes(int32_t sem_mode) {
+    if (sem_mode < 0 || sem_mode > 2) return 0;
+    return sizeof(float) * packed_floats(sem_mode, false);
+}
+extern "C" size_t nsos_mlp_packed_bytes_fold(int32_t sem_mode) {
+    if (sem_mode < 0 || sem_mode > 2) return 0;
+    return sizeof(float) * packed_floats(sem_mode, true);
+}
+extern "C" int32_t nsos_mlp_pack(const nsos_mlp_tensors* T, int32_t sem_mode, void* packed, size_t packed_bytes,
+                                 void* stream) {
+    return pack_impl(T, sem_mode, packed, packed_bytes, stream, false);
+}
+extern "C" int32_t nsos_mlp_pack_fold(const nsos_mlp_tensors* T, int32_t sem_mode, void* packed, size_t packed_bytes,
+                                      void* stream) {
+    return pack_impl(T, sem_mode, packed, packed_bytes, stream, true);
+}
+
+#define NSOS_RAY_ARGS                                                                                                       \
+    const void *packed, int32_t sem_mode, const float *rays_o, const float *rays_d, const float *viewdirs, const float *z_vals, \
+        int64_t n_rays, int32_t n_samples, float *raw
+#define NSOS_RAY_PASS packed, sem_mode, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw
+
+extern "C" int32_t nsos_mlp_forward_rays(NSOS_RAY_ARGS, void* stream) {
+    return forward_rays<false>(NSOS_RAY_PASS, nullptr, stream);
+}
+extern "C" int32_t nsos_mlp_forward_rays_fold(NSOS_RAY_ARGS, void* stream) {
+    return forward_rays<true>(NSOS_RAY_PASS, nullptr, stream);
+}
+extern "C" int32_t nsos_mlp_forward_rays_save(NSOS_RAY_ARGS, float* sem_in, float* sem_hid, void* stream) {
+    return forward_rays_save<false>(NSOS_RAY_PASS, sem_in, sem_hid, stream);
+}
+extern "C" int32_t nsos_mlp_forward_rays_save_fold(NSOS_RAY_ARGS, float* sem_in, float* sem_hid, void* stream) {
+    return forward_rays_save<true>(NSOS_RAY_PASS, sem_in, sem_hid, stream);
+}
+extern "C" int32_t nsos_mlp_forward_rays_save_all(NSOS_RAY_ARGS, float* acts, void* stream) {
+    return forward_rays_save_all<false>(NSOS_RAY_PASS, acts, stream);
+}
+extern "C" int32_t nsos_mlp_forward_rays_save_all_fold(NSOS_RAY_ARGS, float* acts, void* stream) {
+    return forward_rays_save_all<true>(NSOS_RAY_PASS, acts, stream);
+}
+extern "C" int32_t nsos_mlp_profile_rays(NSOS_RAY_ARGS, uint64_t* stamps, void* stream) {
+    if (n_rays == 0) return NSOS_OK;
+    NSOS_REQUIRE(stamps, NSOS_ERR_NULL_POINTER);
+    return forward_rays<false>(NSOS_RAY_PASS, stamps, stream);
+}
+extern "C" int32_t nsos_mlp_profile_rays_fold(NSOS_RAY_ARGS, uint64_t* stamps, void* stream) {
+    if (n_rays == 0) return NSOS_OK;
+    NSOS_REQUIRE(stamps, NSOS_ERR_NULL_POINTER);
+    return forward_rays<true>(NSOS_RAY_PASS, stamps, stream);
+}
+extern "C" int32_t nsos_mlp_forward_points(const void* packed, int32_t sem_mode, const float* pts, const float* dirs,
+                                           int64_t n_pts, float* raw, void* stream) {
+    return forward_points<false>(packed, sem_mode, pts, dirs, n_pts, raw, stream);
+}
+extern "C" int32_t nsos_mlp_forward_points_fold(const void* packed, int32_t sem_mode, const float* pts, const float* dirs,
+                                                int64_t n_pts, float* raw, void* stream) {
+    return forward_points<true>(packed, sem_mode, pts, dirs, n_pts, raw, stream);
 }

@@ -18,8 +18,9 @@ class GraphedRender:
     def __init__(self, net, n_rays: int, near_far: Tuple[float, float], warmup: int = 3, **render_kwargs):
         if net.training:
             raise ValueError("GraphedRender captures the deterministic eval-mode path: call net.eval() first")
-        # Trainable nets re-pack their weight streams on every call (NeRFMLP.packed_weights), so the pack launches are part
-        # of the graph and a replay reads the parameters' CURRENT values; a frozen net's streams are packed once, outside.
+        # Trainable nets re-pack their weight streams on every call (NeRFMLP.packed_weights), so the pack launches -- for the
+        # exact fp32 path the view fold's too (nsos_mlp_pack_fold: two stream-ordered kernels, no allocation, no host sync) -- are
+        # part of the graph and a replay reads the parameters' CURRENT values; a frozen net's streams are packed once, outside.
         self._packs_in_graph = all(any(p.requires_grad for p in m.parameters()) for m in (net.nerf, net.nerf_fine))
         self.net, self.n_rays, self.near_far, self.kw = net, int(n_rays), near_far, render_kwargs
         dev = next(net.parameters()).device

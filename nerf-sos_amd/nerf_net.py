@@ -189,7 +189,11 @@ class NeRFMLP(nn.Module):
         without bumping ``Tensor._version``, so a version-keyed cache would keep rendering -- and differentiating -- the
         initial weights while the optimizer moves the parameters.  A fully frozen net is packed once and re-packed when
         (data_ptr, _version) of a parameter changes (``load_state_dict``, in-place ops); after a ``p.data`` edit of a
-        frozen net call invalidate_packed()."""
+        frozen net call invalidate_packed().
+
+        "fp32_fold" is the exact-fp32 stream NeRFNet's ray path renders from: feature_linear multiplied into views_linears.0 on the
+        device at pack time (ops.PackPlan.run -> nsos_mlp_pack_fold), under the very same caching rule; "fp32" stays the unfolded
+        stream of the point query (forward) and of ops.mlp_forward_rays(fold=False), bit-pinned to the C oracle's chain."""
         named = _named_params(self.mlp)
         params = [p for _, p in named]
         if not self.fast or precision == "generic":     # ("generic": the shipped architecture on the generic kernels -- ray gradients)
@@ -763,17 +767,21 @@ class NeRFNet(nn.Module):
                     return raw
                 return net.query_rays(rays_o, rays_d, viewdirs, z)
             pp = self.pass_precision(tag)
+            # the exact fp32 ray path runs on the FOLDED stream in all three modes (feature_linear multiplied into views_linears.0 at
+            # pack time, DESIGN.md "View fold"): their raw is bit-identical to one another
             if not save:
                 if pp != "fp32":
                     return ops.mlp_forward_rays_lp(net.packed_weights(pp), net.sem_mode, pp, rays_o, rays_d, viewdirs, z)
-                return ops.mlp_forward_rays(net.packed_weights(), net.sem_mode, rays_o, rays_d, viewdirs, z)
+                return ops.mlp_forward_rays(net.packed_weights("fp32_fold"), net.sem_mode, rays_o, rays_d, viewdirs, z, fold=True)
+            stream = lambda prec: net.packed_weights("fp32_fold" if prec == "fp32" else prec)   # noqa: E731
             if save == "all":   # full backward (K7): every layer's activations (exact-fp32 or split-fp16 kernel)
                 prec = self.mlp_precision if self.mlp_precision in ("fp32", "fp16x3") else "fp16x3"    # (see render_rays)
-                raw, acts, masks = ops.mlp_forward_rays_save_all(net.packed_weights(prec), net.sem_mode, rays_o, rays_d, viewdirs, z, prec,
-                                                                 acts16=prec == "fp16x3" and self.compact_activations)
+                raw, acts, masks = ops.mlp_forward_rays_save_all(stream(prec), net.sem_mode, rays_o, rays_d, viewdirs, z, prec,
+                                                                 acts16=prec == "fp16x3" and self.compact_activations, fold=prec == "fp32")
                 saved[tag] = dict(acts=acts, raw=raw, z=z, masks=masks)
                 return raw
-            raw, sem_in, sem_hid = ops.mlp_forward_rays_save(net.packed_weights(pp), net.sem_mode, rays_o, rays_d, viewdirs, z, pp, compact=True)
+            raw, sem_in, sem_hid = ops.mlp_forward_rays_save(stream(pp), net.sem_mode, rays_o, rays_d, viewdirs, z, pp, compact=True,
+                                                             fold=pp == "fp32")
             saved[tag] = dict(sem_in=sem_in, sem_hid=sem_hid, precision=pp)
             return raw
 

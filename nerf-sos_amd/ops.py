@@ -121,12 +121,15 @@ _MLP_FIELDS = (("alpha", "alpha_linear"), ("feature", "feature_linear"), ("views
 
 
 DTYPES = {"fp32": 0, "fp16": 1, "bf16": 2, "fp16x3": 3,   # fp16x3: split-fp16 operands, fp32-accurate results (K2-X3)
-          "fp16x3_bwd": 4}                                  # the transposed stream of the fused input-gradient kernel (K7-X3)
+          "fp16x3_bwd": 4,                                  # the transposed stream of the fused input-gradient kernel (K7-X3)
+          "fp32_fold": 5}   # the fp32 stream with feature_linear folded into views_linears.0 (nsos_mlp_pack_fold): mlp_forward_rays*(fold=True)
 
 
 def packed_bytes(sem_mode: int, precision: str = "fp32") -> int:
     if precision == "fp32":
         return int(_lib.lib().nsos_mlp_packed_bytes(sem_mode))
+    if precision == "fp32_fold":
+        return int(_lib.lib().nsos_mlp_packed_bytes_fold(sem_mode))
     if precision == "fp16x3":
         return int(_lib.lib().nsos_mlp_packed_bytes_x3(sem_mode))
     if precision == "fp16x3_bwd":
@@ -182,6 +185,8 @@ class PackPlan:
         T, L = C.byref(self.tensors), _lib.lib()
         if precision == "fp32":
             _lib.check(L.nsos_mlp_pack(T, self.sem_mode, _p(out), nbytes, _stream()), "nsos_mlp_pack")
+        elif precision == "fp32_fold":   # two launches: the fold (W' = W_v[:, :256] W_f, b') into the buffer's own tail, then the pack
+            _lib.check(L.nsos_mlp_pack_fold(T, self.sem_mode, _p(out), nbytes, _stream()), "nsos_mlp_pack_fold")
         elif precision == "fp16x3":
             _lib.check(L.nsos_mlp_pack_x3(T, self.sem_mode, _p(out), nbytes, _stream()), "nsos_mlp_pack_x3")
         elif precision == "fp16x3_bwd":
@@ -499,8 +504,10 @@ def pack_mlp(params: Dict[str, torch.Tensor], sem_mode: int, out: Optional[torch
 
 
 def mlp_forward_rays(packed: torch.Tensor, sem_mode: int, rays_o: torch.Tensor, rays_d: torch.Tensor,
-                     viewdirs: torch.Tensor, z_vals: torch.Tensor) -> torch.Tensor:
-    """raw [R,S,C] for the points o + d*z of each ray  (models/nerf_mlp.py:67-100,179-215)."""
+                     viewdirs: torch.Tensor, z_vals: torch.Tensor, fold: bool = False) -> torch.Tensor:
+    """raw [R,S,C] for the points o + d*z of each ray  (models/nerf_mlp.py:67-100,179-215).
+    fold: `packed` is the folded stream (pack_mlp(..., precision="fp32_fold")): feature_linear multiplied into views_linears.0
+    at pack time, 11 % fewer MFMAs; sigma / semantics bit-identical to the unfolded kernel, rgb equal up to rounding."""
     rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
     viewdirs, z_vals = _dev(viewdirs, "viewdirs"), _dev(z_vals, "z_vals")
     R, S = z_vals.shape
@@ -510,12 +517,40 @@ def mlp_forward_rays(packed: torch.Tensor, sem_mode: int, rays_o: torch.Tensor, 
     if KERNEL_EVENTS is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
-    _lib.check(_lib.lib().nsos_mlp_forward_rays(_p(packed), sem_mode, _p(rays_o), _p(rays_d), _p(viewdirs),
-                                                _p(z_vals), R, S, _p(raw), _stream()), "nsos_mlp_forward_rays")
+    fn = _lib.lib().nsos_mlp_forward_rays_fold if fold else _lib.lib().nsos_mlp_forward_rays
+    _lib.check(fn(_p(_fold_checked(packed, sem_mode, fold)), sem_mode, _p(rays_o), _p(rays_d), _p(viewdirs),
+                  _p(z_vals), R, S, _p(raw), _stream()), "nsos_mlp_forward_rays_fold" if fold else "nsos_mlp_forward_rays")
     if ev is not None:
         ev[1].record()
         KERNEL_EVENTS.append((R * S, ev[0], ev[1]))
     return raw
+
+
+def _fold_checked(packed: torch.Tensor, sem_mode: int, fold: bool) -> torch.Tensor:
+    """The folded and the unfolded stream hold the view and feature chunks in different order, and nothing in the buffers but
+    their SIZE tells them apart (the folded one carries the fold's scratch region behind the chunks): refuse an unfolded buffer
+    where a folded one is due, and a buffer of exactly the folded size where the unfolded kernels would read it."""
+    nbytes = packed.numel() * packed.element_size()
+    if fold and nbytes < packed_bytes(sem_mode, "fp32_fold"):
+        raise ValueError("fold=True needs the folded stream: pack_mlp(..., precision='fp32_fold') / packed_weights('fp32_fold')")
+    if not fold and nbytes == packed_bytes(sem_mode, "fp32_fold"):
+        raise ValueError("this buffer has the size of the folded stream (precision='fp32_fold'): pass fold=True, or pack with precision='fp32'")
+    return packed
+
+
+def mlp_profile_rays(packed: torch.Tensor, sem_mode: int, rays_o: torch.Tensor, rays_d: torch.Tensor, viewdirs: torch.Tensor,
+                     z_vals: torch.Tensor, fold: bool = False):
+    """Diagnostics: mlp_forward_rays plus the per-phase shader-clock stamps of the first tile of workgroups 0..3
+    (nsos_mlp_profile_rays[_fold]): (raw [R,S,C], stamps int64 [16 waves, 64 slots]); slot meaning: scripts/phase_profile.py."""
+    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
+    viewdirs, z_vals = _dev(viewdirs, "viewdirs"), _dev(z_vals, "z_vals")
+    R, S = z_vals.shape
+    raw = torch.empty((R, S, 4 if sem_mode == SEM_NONE else 6), device=z_vals.device, dtype=torch.float32)
+    stamps = torch.zeros((16, 64), device=z_vals.device, dtype=torch.int64)
+    fn = _lib.lib().nsos_mlp_profile_rays_fold if fold else _lib.lib().nsos_mlp_profile_rays
+    _lib.check(fn(_p(_fold_checked(packed, sem_mode, fold)), sem_mode, _p(rays_o), _p(rays_d), _p(viewdirs), _p(z_vals), R, S, _p(raw),
+                  _p(stamps), _stream()), "nsos_mlp_profile_rays_fold" if fold else "nsos_mlp_profile_rays")
+    return raw, stamps
 
 
 def lp_selected_kernel() -> int:
@@ -552,12 +587,15 @@ def mlp_forward_rays_lp(packed: torch.Tensor, sem_mode: int, precision: str, ray
 
 
 def mlp_forward_rays_save(packed: torch.Tensor, sem_mode: int, rays_o: torch.Tensor, rays_d: torch.Tensor,
-                          viewdirs: torch.Tensor, z_vals: torch.Tensor, precision: str = "fp32", compact: bool = False):
+                          viewdirs: torch.Tensor, z_vals: torch.Tensor, precision: str = "fp32", compact: bool = False,
+                          fold: bool = False):
     """Training-mode K2 (frozen backbone): raw [R,S,6] plus the semantic head's saved inputs
     sem_in [R*S,320] = [relu(h7) | x63 | 1] and sem_hid [R*S,128] (see nsos_mlp_forward_rays_save[_lp]).
     `packed` must have been packed for the same `precision`.  compact (16-bit precisions only): sem_in AND sem_hid come back
     in the precision's own 16-bit dtype (sem_in's values are 16-bit anyway; sem_hid is rounded): 896 B per point instead of
-    1792 to store and to read back in sem_head_wgrad."""
+    1792 to store and to read back in sem_head_wgrad.  fold (fp32 only): the folded stream, as in mlp_forward_rays."""
+    if fold and precision != "fp32":
+        raise NotImplementedError("the folded stream exists for the exact fp32 kernel only")
     if sem_mode == SEM_NONE:
         raise ValueError("mlp_forward_rays_save needs a semantic head")
     rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
@@ -581,9 +619,10 @@ def mlp_forward_rays_save(packed: torch.Tensor, sem_mode: int, rays_o: torch.Ten
         sem_hid = torch.empty((R * S, 128), device=dev, dtype=sem_in.dtype if compact else torch.float32)
     ev = _ev_begin()
     if precision == "fp32":
-        _lib.check(_lib.lib().nsos_mlp_forward_rays_save(_p(packed), sem_mode, _p(rays_o), _p(rays_d), _p(viewdirs),
-                                                         _p(z_vals), R, S, _p(raw), _p(sem_in), _p(sem_hid), _stream()),
-                   "nsos_mlp_forward_rays_save")
+        fn = _lib.lib().nsos_mlp_forward_rays_save_fold if fold else _lib.lib().nsos_mlp_forward_rays_save
+        _lib.check(fn(_p(_fold_checked(packed, sem_mode, fold)), sem_mode, _p(rays_o), _p(rays_d), _p(viewdirs),
+                      _p(z_vals), R, S, _p(raw), _p(sem_in), _p(sem_hid), _stream()),
+                   "nsos_mlp_forward_rays_save_fold" if fold else "nsos_mlp_forward_rays_save")
     elif precision == "fp16x3":
         _lib.check(_lib.lib().nsos_mlp_forward_rays_save_x3(_p(packed), sem_mode, _p(rays_o), _p(rays_d), _p(viewdirs),
                                                             _p(z_vals), R, S, _p(raw), _p(sem_in), _p(sem_hid), _stream()),
@@ -719,16 +758,18 @@ def sem_head_wgrad(weights: torch.Tensor, g_semantics: torch.Tensor, sem2_w: tor
     return out
 
 
-def mlp_forward_points(packed: torch.Tensor, sem_mode: int, pts: torch.Tensor, dirs: torch.Tensor) -> torch.Tensor:
-    """raw [P,C] for explicit points / per-point directions  (NeRFMLP.forward, models/nerf_mlp.py:179)."""
+def mlp_forward_points(packed: torch.Tensor, sem_mode: int, pts: torch.Tensor, dirs: torch.Tensor, fold: bool = False) -> torch.Tensor:
+    """raw [P,C] for explicit points / per-point directions  (NeRFMLP.forward, models/nerf_mlp.py:179).
+    fold: the folded stream, as in mlp_forward_rays."""
     pts, dirs = _dev(pts, "pts"), _dev(dirs, "viewdirs")
     P = pts.shape[0]
     if tuple(pts.shape) != (P, 3) or tuple(dirs.shape) != (P, 3):
         raise ValueError(f"pts / viewdirs must both be [P,3], got {tuple(pts.shape)} / {tuple(dirs.shape)}")
     Cn = 4 if sem_mode == SEM_NONE else 6
     raw = torch.empty((P, Cn), device=pts.device, dtype=torch.float32)
-    _lib.check(_lib.lib().nsos_mlp_forward_points(_p(packed), sem_mode, _p(pts), _p(dirs), P, _p(raw), _stream()),
-               "nsos_mlp_forward_points")
+    fn = _lib.lib().nsos_mlp_forward_points_fold if fold else _lib.lib().nsos_mlp_forward_points
+    _lib.check(fn(_p(_fold_checked(packed, sem_mode, fold)), sem_mode, _p(pts), _p(dirs), P, _p(raw), _stream()),
+               "nsos_mlp_forward_points_fold" if fold else "nsos_mlp_forward_points")
     return raw
 
 
@@ -1020,9 +1061,14 @@ ACTS_FEAT, ACTS_VIEWS, ACTS_SEM, ACTS_X, ACTS_D, ACTS_DIM = 2048, 2304, 2432, 25
 
 
 def mlp_forward_rays_save_all(packed: torch.Tensor, sem_mode: int, rays_o: torch.Tensor, rays_d: torch.Tensor,
-                              viewdirs: torch.Tensor, z_vals: torch.Tensor, precision: str = "fp32", acts16: bool = False):
+                              viewdirs: torch.Tensor, z_vals: torch.Tensor, precision: str = "fp32", acts16: bool = False,
+                              fold: bool = False):
     """Training-mode K2 with every layer's activations stored: (raw [R,S,C], acts [R*S, ACTS_DIM], relu bit masks or None).
-    precision "fp32" (exact kernel) or "fp16x3" (split-fp16 kernel, fp32-accurate); `packed` must match."""
+    precision "fp32" (exact kernel) or "fp16x3" (split-fp16 kernel, fp32-accurate); `packed` must match.  fold (fp32 only): the
+    folded stream, as in mlp_forward_rays -- the views block of acts comes from the folded chain, the feature block is still
+    feature_linear(h7)."""
+    if fold and precision != "fp32":
+        raise NotImplementedError("the folded stream exists for the exact fp32 kernel only")
     if precision not in ("fp32", "fp16x3"):
         raise NotImplementedError("the full backward needs fp32-accurate activations: precision 'fp32' or 'fp16x3'")
     rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
@@ -1042,8 +1088,9 @@ def mlp_forward_rays_save_all(packed: torch.Tensor, sem_mode: int, rays_o: torch
                    "nsos_mlp_forward_rays_save_all_x3")
         _ev_end(ev, R * S)
         return raw, acts, masks
-    _lib.check(_lib.lib().nsos_mlp_forward_rays_save_all(_p(packed), sem_mode, _p(rays_o), _p(rays_d), _p(viewdirs), _p(z_vals),
-                                                         R, S, _p(raw), _p(acts), _stream()), "nsos_mlp_forward_rays_save_all")
+    fn = _lib.lib().nsos_mlp_forward_rays_save_all_fold if fold else _lib.lib().nsos_mlp_forward_rays_save_all
+    _lib.check(fn(_p(_fold_checked(packed, sem_mode, fold)), sem_mode, _p(rays_o), _p(rays_d), _p(viewdirs), _p(z_vals),
+                  R, S, _p(raw), _p(acts), _stream()), "nsos_mlp_forward_rays_save_all_fold" if fold else "nsos_mlp_forward_rays_save_all")
     _ev_end(ev, R * S)
     return raw, acts, None
 

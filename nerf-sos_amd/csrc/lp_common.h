@@ -2,6 +2,7 @@
 // number formats, the accumulator -> packed-B-operand conversion, parameters, encoding slices, VALU heads.
 #pragma once
 #include "mlp_common.h"
+#include "mlp_host.h"
 
 namespace nsos {
 namespace lp {
@@ -198,8 +199,22 @@ __device__ __forceinline__ void heads_partial_f32(const f32x16 (&h)[NT], const f
         }
 }
 
+// sem_mode x dtype x SAVE of the three 16-bit kernels: f(T{}, SEM, SAVE) with the number-format class and two integral constants.
+// The training variants (SAVE) store the semantic head's inputs: there is none for NSOS_SEM_NONE.
+template <class F>
+int32_t dispatch_lp(int32_t sem_mode, int32_t dtype, bool save, F&& f) {
+    return nsos_dispatch_sem(sem_mode, [&](auto sem) -> int32_t {
+        return nsos_dispatch_dtype<F16, BF16>(dtype, [&](auto t) -> int32_t {
+            return nsos_dispatch_bool(save, [&](auto sv) -> int32_t {
+                if constexpr (decltype(sem)::value == 0 && decltype(sv)::value != 0) return NSOS_ERR_UNSUPPORTED;
+                else return f(t, sem, sv);
+            });
+        });
+    });
+}
+
 // mlp_lp8.hip: the two-waves-per-SIMD kernel (8 waves x 32 points per 256-point tile), same packed stream and results
-int32_t launch_lp8(const LpParams& p, int32_t sem_mode, bool is_f16, bool save, hipStream_t stream);
+int32_t launch_lp8(const LpParams& p, int32_t sem_mode, int32_t dtype, bool save, hipStream_t stream);
 
 // mlp_lp16.hip: the same workgroup shape on v_mfma_f32_16x16x32 (its own packed stream: p.chunks points at it)
 __host__ __device__ constexpr int lp16_chunks(int sem) {
@@ -210,7 +225,7 @@ __host__ __device__ constexpr int lp16_chunks(int sem) {
 // activations), which the kernel keeps resident in LDS instead of streaming them as a chunk of their own
 constexpr int kLp16TailBytes = 4096;
 __host__ __device__ constexpr size_t lp16_stream_bytes(int sem) { return (size_t)lp16_chunks(sem) * kSlotBytes + kLp16TailBytes; }
-int32_t launch_lp16(const LpParams& p, int32_t sem_mode, bool is_f16, bool save, hipStream_t stream);
+int32_t launch_lp16(const LpParams& p, int32_t sem_mode, int32_t dtype, bool save, hipStream_t stream);
 int32_t pack_lp16(const void* tensors, int32_t sem_mode, bool is_f16, unsigned char* chunks, hipStream_t stream, bool heads_only = false);
 
 }  // namespace lp

@@ -32,6 +32,7 @@
 //     first chunks overlaps the current tile's tail.
 // Compiled with -ffp-contract=off (x = o + d*z must stay a separately rounded multiply and add).
 #include "mlp_common.h"
+#include "mlp_host.h"
 
 using namespace nsos;
 
@@ -572,51 +573,16 @@ __global__ __launch_bounds__(256) void pack_kernel(const PackParams P) {
     P.chunks[gid] = v;
 }
 
-int num_cus() { return nsos_device_cus(); }
-
 constexpr int kLdsBytes = 3 * kSlotFloats * 4;
 
-template <int SEM, bool RAYS, int SAVE = 0, bool FOLD = false>
-int32_t launch_mlp(const MlpParams& p, hipStream_t stream) {
-    static NsosPerDeviceFlag configured_on;
-    bool& configured = configured_on.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<SEM, RAYS, SAVE, FOLD>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        if (e != hipSuccess) return (int32_t)e;
-        configured = true;
-    }
-    const int grid = p.n_tiles < num_cus() ? p.n_tiles : num_cus();
-    hipLaunchKernelGGL((mlp_fused_kernel<SEM, RAYS, SAVE, FOLD>), dim3(grid), dim3(256), kLdsBytes, stream, p);
-    return nsos_launch_status();
-}
-
+// sem_mode x RAYS x SAVE x FOLD -> the kernel.  SAVE 1 stores the semantic head's inputs: there is none without a head.
 template <bool RAYS, int SAVE = 0, bool FOLD = false>
 int32_t dispatch_mlp(int sem_mode, const MlpParams& p, hipStream_t stream) {
-    switch (sem_mode) {
-        case NSOS_SEM_NONE:
-            if constexpr (SAVE != 1) return launch_mlp<0, RAYS, SAVE, FOLD>(p, stream);
-            break;
-        case NSOS_SEM_PLAIN: return launch_mlp<1, RAYS, SAVE, FOLD>(p, stream);
-        case NSOS_SEM_COORD: return launch_mlp<2, RAYS, SAVE, FOLD>(p, stream);
-    }
-    return NSOS_ERR_UNSUPPORTED;
-}
-
-int32_t fill_ray_params(MlpParams& p, const void* packed, const float* rays_o, const float* rays_d,
-                        const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples, float* raw) {
-    NSOS_REQUIRE(packed && rays_o && rays_d && viewdirs && z_vals && raw, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(n_rays >= 0 && n_samples >= 1, NSOS_ERR_BAD_SHAPE);
-    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)raw & 15) == 0, NSOS_ERR_MISALIGNED);
-    const long long n_pts = (long long)n_rays * n_samples;
-    NSOS_REQUIRE((n_pts + kTilePts - 1) / kTilePts < (1ll << 31), NSOS_ERR_UNSUPPORTED);
-    p = MlpParams{};
-    p.aux = static_cast<const float*>(packed);
-    p.chunks = p.aux + kAuxFloats;
-    p.rays_o = rays_o; p.rays_d = rays_d; p.viewdirs = viewdirs; p.z_vals = z_vals;
-    p.raw = raw; p.n_pts = n_pts; p.n_samples = n_samples;
-    p.n_tiles = (int)((n_pts + kTilePts - 1) / kTilePts);
-    return NSOS_OK;
+    return nsos_dispatch_sem(sem_mode, [&](auto sem) -> int32_t {
+        constexpr int SEM = decltype(sem)::value;
+        if constexpr (SEM == 0 && SAVE == 1) return NSOS_ERR_UNSUPPORTED;
+        else return nsos_launch_persistent<&mlp_fused_kernel<SEM, RAYS, SAVE, FOLD>>(p, p.n_tiles, 256, kLdsBytes, stream);
+    });
 }
 
 size_t packed_floats(int sem_mode, bool fold) {
@@ -624,14 +590,8 @@ size_t packed_floats(int sem_mode, bool fold) {
 }
 
 int32_t pack_impl(const nsos_mlp_tensors* T, int32_t sem_mode, void* packed, size_t packed_bytes, void* stream, bool fold) {
-    NSOS_REQUIRE(T && packed, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(sem_mode >= 0 && sem_mode <= 2, NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(packed_bytes >= sizeof(float) * packed_floats(sem_mode, fold), NSOS_ERR_BUFFER_TOO_SMALL);
-    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0, NSOS_ERR_MISALIGNED);
-    for (int l = 0; l < NSOS_NET_DEPTH; ++l) NSOS_REQUIRE(T->pts_w[l] && T->pts_b[l], NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(T->alpha_w && T->alpha_b && T->feature_w && T->feature_b && T->views_w && T->views_b &&
-                     T->rgb_w && T->rgb_b, NSOS_ERR_NULL_POINTER);
-    if (sem_mode) NSOS_REQUIRE(T->sem0_w && T->sem0_b && T->sem2_w && T->sem2_b, NSOS_ERR_NULL_POINTER);
+    const int32_t ok = nsos_check_pack(T, sem_mode, nsos_sem_mode_ok(sem_mode), packed, packed_bytes, sizeof(float) * packed_floats(sem_mode, fold));
+    if (ok != NSOS_OK) return ok;
 
     PackParams P = {};
     int n = 0;
@@ -679,46 +639,45 @@ int32_t pack_impl(const nsos_mlp_tensors* T, int32_t sem_mode, void* packed, siz
     return nsos_launch_status();
 }
 
-// The entry points' bodies; FOLD: the folded stream of nsos_mlp_pack_fold and the kernels that consume it.
-template <bool FOLD>
-int32_t forward_rays(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d, const float* viewdirs,
-                     const float* z_vals, int64_t n_rays, int32_t n_samples, float* raw, uint64_t* stamps, void* stream) {
-    if (n_rays == 0) return NSOS_OK;  // empty batch: nothing to launch (empty tensors have NULL data pointers)
-    MlpParams p;
-    const int32_t rc = fill_ray_params(p, packed, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw);
+// The ray entry points' common tail; `p` arrives with the outputs the variant adds.  FOLD: the folded stream of nsos_mlp_pack_fold
+// and the kernels that consume it.  (sem_mode is checked last here, by the dispatch.)
+template <int SAVE, bool FOLD>
+int32_t forward_rays(const NsosRayCall& c, int32_t sem_mode, MlpParams p, void* stream) {
+    int32_t rc = nsos_check_ray_call(c, false, true);
+    if (rc == NSOS_OK) rc = nsos_fill_ray_call(p, c, kTilePts);
     if (rc != NSOS_OK) return rc;
-    p.prof = reinterpret_cast<unsigned long long*>(stamps);  // diagnostics (nsos_mlp_profile_rays[_fold]), else NULL
-    return dispatch_mlp<true, 0, FOLD>(sem_mode, p, (hipStream_t)stream);
+    p.aux = static_cast<const float*>(c.packed);
+    p.chunks = p.aux + kAuxFloats;
+    return dispatch_mlp<true, SAVE, FOLD>(sem_mode, p, (hipStream_t)stream);
 }
 
 template <bool FOLD>
-int32_t forward_rays_save(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
-                          const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples, float* raw,
-                          float* sem_in, float* sem_hid, void* stream) {
-    if (n_rays == 0) return NSOS_OK;
-    NSOS_REQUIRE(sem_in && sem_hid, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(sem_mode == NSOS_SEM_PLAIN || sem_mode == NSOS_SEM_COORD, NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(((uintptr_t)sem_in & 15) == 0 && ((uintptr_t)sem_hid & 15) == 0, NSOS_ERR_MISALIGNED);
-    MlpParams p;
-    const int32_t rc = fill_ray_params(p, packed, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw);
+int32_t forward_rays_plain(const NsosRayCall& c, int32_t sem_mode, uint64_t* stamps, void* stream) {
+    if (c.n_rays == 0) return NSOS_OK;  // empty batch: nothing to launch (empty tensors have NULL data pointers)
+    MlpParams p = {};
+    p.prof = reinterpret_cast<unsigned long long*>(stamps);  // diagnostics (nsos_mlp_profile_rays[_fold]), else NULL
+    return forward_rays<0, FOLD>(c, sem_mode, p, stream);
+}
+
+template <bool FOLD>
+int32_t forward_rays_save(const NsosRayCall& c, int32_t sem_mode, float* sem_in, float* sem_hid, void* stream) {
+    if (c.n_rays == 0) return NSOS_OK;
+    const int32_t rc = nsos_check_outputs({sem_in, sem_hid}, sem_mode == NSOS_SEM_PLAIN || sem_mode == NSOS_SEM_COORD);
     if (rc != NSOS_OK) return rc;
+    MlpParams p = {};
     p.sem_in = sem_in;
     p.sem_hid = sem_hid;
-    return dispatch_mlp<true, 1, FOLD>(sem_mode, p, (hipStream_t)stream);
+    return forward_rays<1, FOLD>(c, sem_mode, p, stream);
 }
 
 template <bool FOLD>
-int32_t forward_rays_save_all(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
-                              const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples, float* raw,
-                              float* acts, void* stream) {
-    if (n_rays == 0) return NSOS_OK;
-    NSOS_REQUIRE(acts, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(((uintptr_t)acts & 15) == 0, NSOS_ERR_MISALIGNED);
-    MlpParams p;
-    const int32_t rc = fill_ray_params(p, packed, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw);
+int32_t forward_rays_save_all(const NsosRayCall& c, int32_t sem_mode, float* acts, void* stream) {
+    if (c.n_rays == 0) return NSOS_OK;
+    const int32_t rc = nsos_check_outputs({acts});
     if (rc != NSOS_OK) return rc;
+    MlpParams p = {};
     p.acts = acts;
-    return dispatch_mlp<true, 2, FOLD>(sem_mode, p, (hipStream_t)stream);
+    return forward_rays<2, FOLD>(c, sem_mode, p, stream);
 }
 
 template <bool FOLD>
@@ -727,13 +686,13 @@ int32_t forward_points(const void* packed, int32_t sem_mode, const float* pts, c
     if (n_pts == 0) return NSOS_OK;  // empty batch: nothing to launch (empty tensors have NULL data pointers)
     NSOS_REQUIRE(packed && pts && dirs && raw, NSOS_ERR_NULL_POINTER);
     NSOS_REQUIRE(n_pts >= 0, NSOS_ERR_BAD_SHAPE);
-    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)raw & 15) == 0, NSOS_ERR_MISALIGNED);
-    NSOS_REQUIRE((n_pts + kTilePts - 1) / kTilePts < (1ll << 31), NSOS_ERR_UNSUPPORTED);
+    NSOS_REQUIRE(nsos_aligned16({packed, raw}), NSOS_ERR_MISALIGNED);
     MlpParams p = {};
+    const int32_t rc = nsos_fill_points(p, n_pts, kTilePts);
+    if (rc != NSOS_OK) return rc;
     p.aux = static_cast<const float*>(packed);
     p.chunks = p.aux + kAuxFloats;
-    p.pts = pts; p.dirs = dirs; p.raw = raw; p.n_pts = n_pts; p.n_samples = 1;
-    p.n_tiles = (int)((n_pts + kTilePts - 1) / kTilePts);
+    p.pts = pts; p.dirs = dirs; p.raw = raw; p.n_samples = 1;
     return dispatch_mlp<false, 0, FOLD>(sem_mode, p, (hipStream_t)stream);
 }
 
@@ -760,13 +719,13 @@ extern "C" int32_t nsos_mlp_pack_fold(const nsos_mlp_tensors* T, int32_t sem_mod
 #define NSOS_RAY_ARGS                                                                                                       \
     const void *packed, int32_t sem_mode, const float *rays_o, const float *rays_d, const float *viewdirs, const float *z_vals, \
         int64_t n_rays, int32_t n_samples, float *raw
-#define NSOS_RAY_PASS packed, sem_mode, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw
+#define NSOS_RAY_PASS NsosRayCall{packed, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw}, sem_mode
 
 extern "C" int32_t nsos_mlp_forward_rays(NSOS_RAY_ARGS, void* stream) {
-    return forward_rays<false>(NSOS_RAY_PASS, nullptr, stream);
+    return forward_rays_plain<false>(NSOS_RAY_PASS, nullptr, stream);
 }
 extern "C" int32_t nsos_mlp_forward_rays_fold(NSOS_RAY_ARGS, void* stream) {
-    return forward_rays<true>(NSOS_RAY_PASS, nullptr, stream);
+    return forward_rays_plain<true>(NSOS_RAY_PASS, nullptr, stream);
 }
 extern "C" int32_t nsos_mlp_forward_rays_save(NSOS_RAY_ARGS, float* sem_in, float* sem_hid, void* stream) {
     return forward_rays_save<false>(NSOS_RAY_PASS, sem_in, sem_hid, stream);
@@ -783,12 +742,12 @@ extern "C" int32_t nsos_mlp_forward_rays_save_all_fold(NSOS_RAY_ARGS, float* act
 extern "C" int32_t nsos_mlp_profile_rays(NSOS_RAY_ARGS, uint64_t* stamps, void* stream) {
     if (n_rays == 0) return NSOS_OK;
     NSOS_REQUIRE(stamps, NSOS_ERR_NULL_POINTER);
-    return forward_rays<false>(NSOS_RAY_PASS, stamps, stream);
+    return forward_rays_plain<false>(NSOS_RAY_PASS, stamps, stream);
 }
 extern "C" int32_t nsos_mlp_profile_rays_fold(NSOS_RAY_ARGS, uint64_t* stamps, void* stream) {
     if (n_rays == 0) return NSOS_OK;
     NSOS_REQUIRE(stamps, NSOS_ERR_NULL_POINTER);
-    return forward_rays<true>(NSOS_RAY_PASS, stamps, stream);
+    return forward_rays_plain<true>(NSOS_RAY_PASS, stamps, stream);
 }
 extern "C" int32_t nsos_mlp_forward_points(const void* packed, int32_t sem_mode, const float* pts, const float* dirs,
                                            int64_t n_pts, float* raw, void* stream) {

@@ -445,18 +445,7 @@ constexpr int kLdsBytes = kSlots * kSlotBytes + kAuxWords * 4;
 
 template <class T, int SEM, bool SAVE = false>
 int32_t launch_lp(const LpParams& p, hipStream_t stream) {
-    static NsosPerDeviceFlag configured_on;
-    bool& configured = configured_on.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_lp_kernel<T, SEM, SAVE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        if (e != hipSuccess) return (int32_t)e;
-        configured = true;
-    }
-    const int cus = nsos_device_cus();
-    const int grid = p.n_tiles < cus ? p.n_tiles : cus;
-    hipLaunchKernelGGL((mlp_lp_kernel<T, SEM, SAVE>), dim3(grid), dim3(256), kLdsBytes, stream, p);
-    return nsos_launch_status();
+    return nsos_launch_persistent<&mlp_lp_kernel<T, SEM, SAVE>>(p, p.n_tiles, 256, kLdsBytes, stream);
 }
 
 }  // namespace
@@ -492,14 +481,9 @@ extern "C" int32_t nsos_mlp_pack_lp_heads(const nsos_mlp_tensors* T_, int32_t se
 }
 static int32_t pack_lp_impl(const nsos_mlp_tensors* T_, int32_t sem_mode, int32_t dtype, void* packed, size_t packed_bytes, void* stream,
                             bool heads_only) {
-    NSOS_REQUIRE(T_ && packed, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(sem_mode >= 0 && sem_mode <= 2 && (dtype == NSOS_DTYPE_F16 || dtype == NSOS_DTYPE_BF16), NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(packed_bytes >= nsos_mlp_packed_bytes_lp(sem_mode), NSOS_ERR_BUFFER_TOO_SMALL);
-    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0, NSOS_ERR_MISALIGNED);
-    for (int l = 0; l < NSOS_NET_DEPTH; ++l) NSOS_REQUIRE(T_->pts_w[l] && T_->pts_b[l], NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(T_->alpha_w && T_->alpha_b && T_->feature_w && T_->feature_b && T_->views_w && T_->views_b &&
-                     T_->rgb_w && T_->rgb_b, NSOS_ERR_NULL_POINTER);
-    if (sem_mode) NSOS_REQUIRE(T_->sem0_w && T_->sem0_b && T_->sem2_w && T_->sem2_b, NSOS_ERR_NULL_POINTER);
+    const int32_t ok = nsos_check_pack(T_, sem_mode, nsos_sem_mode_ok(sem_mode) && nsos_dtype16_ok(dtype), packed, packed_bytes,
+                                       nsos_mlp_packed_bytes_lp(sem_mode));
+    if (ok != NSOS_OK) return ok;
 
     const int X = NSOS_XYZ_DIM, W = NSOS_NET_WIDTH;
     const int selected = lp_waves_per_simd();
@@ -586,68 +570,47 @@ extern "C" int32_t nsos_mlp_lp_select_kernel(int32_t waves_per_simd) {
     return NSOS_OK;
 }
 
-static int32_t forward_rays_lp(const void* packed, int32_t sem_mode, int32_t dtype, const float* rays_o,
-                               const float* rays_d, const float* viewdirs, const float* z_vals, int64_t n_rays,
-                               int32_t n_samples, float* raw, unsigned long long* prof, float* sem_in, float* sem_hid,
-                               void* stream, unsigned* sem_in16 = nullptr, unsigned* sem_hid16 = nullptr) {
-    if (n_rays == 0) return NSOS_OK;
-    NSOS_REQUIRE(packed && rays_o && rays_d && viewdirs && z_vals && raw, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(n_rays > 0 && n_samples >= 1, NSOS_ERR_BAD_SHAPE);
-    NSOS_REQUIRE(n_rays < (1ll << 31), NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(sem_mode >= 0 && sem_mode <= 2 && (dtype == NSOS_DTYPE_F16 || dtype == NSOS_DTYPE_BF16), NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)raw & 15) == 0, NSOS_ERR_MISALIGNED);
-    const long long n_pts = (long long)n_rays * n_samples;
-    NSOS_REQUIRE((n_pts + kTilePts - 1) / kTilePts < (1ll << 31), NSOS_ERR_UNSUPPORTED);
+static int32_t forward_rays_lp(const NsosRayCall& c, int32_t sem_mode, int32_t dtype, unsigned long long* prof, float* sem_in,
+                               float* sem_hid, void* stream, unsigned* sem_in16 = nullptr, unsigned* sem_hid16 = nullptr) {
+    if (c.n_rays == 0) return NSOS_OK;
     LpParams p = {};
-    p.aux = static_cast<const unsigned*>(packed);
+    int32_t rc = nsos_check_ray_call(c, true, nsos_sem_mode_ok(sem_mode) && nsos_dtype16_ok(dtype));
+    if (rc == NSOS_OK) rc = nsos_fill_ray_call(p, c, kTilePts);
+    if (rc != NSOS_OK) return rc;
+    p.aux = static_cast<const unsigned*>(c.packed);
     p.chunks = reinterpret_cast<const unsigned char*>(p.aux + kAuxWords);
-    p.rays_o = rays_o; p.rays_d = rays_d; p.viewdirs = viewdirs; p.z_vals = z_vals;
-    p.raw = raw; p.n_pts = n_pts; p.n_samples = n_samples;
-    p.n_tiles = (int)((n_pts + kTilePts - 1) / kTilePts);
     p.prof = prof ? prof : g_lp_stamps;
     p.sem_in = sem_in;
     p.sem_in16 = sem_in16;
     p.sem_hid = sem_hid;
     p.sem_hid16 = sem_hid16;
     const hipStream_t st = (hipStream_t)stream;
+    const bool save = sem_in || sem_in16;   // the training variants need a semantic head and the matching second output
+    if (save) NSOS_REQUIRE((sem_in16 ? (void*)sem_hid16 : (void*)sem_hid) && sem_mode != NSOS_SEM_NONE, NSOS_ERR_UNSUPPORTED);
     // NSOS_LP_WAVES=4 selects the one-wave-per-SIMD kernel of round 1 (A/B measurements); default: two waves per SIMD
     // (mlp_lp8_kernel indexes its points with 32 bits: launches of 2^31 points or more -- 11 M rays x 192 samples -- take the
     //  round-1 kernel, whose results are bit-identical)
     // (its training variant stores the compact 16-bit operands only: the fp32 sem_in / sem_hid of nsos_mlp_forward_rays_save_lp
     //  -- tests and the exact-kernel backward -- come from the round-1 kernel as well)
-    if (lp_waves_per_simd() >= 2 && n_pts < (1ll << 31) && !(sem_in && !sem_in16)) {
-        if (sem_in || sem_in16) NSOS_REQUIRE((sem_in16 ? (void*)sem_hid16 : (void*)sem_hid) && sem_mode != NSOS_SEM_NONE, NSOS_ERR_UNSUPPORTED);
+    if (lp_waves_per_simd() >= 2 && p.n_pts < (1ll << 31) && !(sem_in && !sem_in16)) {
         if (lp_waves_per_simd() == 3) {
             p.chunks += 2 * (size_t)lp_chunks(sem_mode) * kSlotBytes;   // the third stream: 16x16x32 tiles
-            return launch_lp16(p, sem_mode, dtype == NSOS_DTYPE_F16, sem_in || sem_in16, st);
+            return launch_lp16(p, sem_mode, dtype, save, st);
         }
         p.chunks += (size_t)lp_chunks(sem_mode) * kSlotBytes;   // the second stream: tile-pair-major hidden layers
-        return launch_lp8(p, sem_mode, dtype == NSOS_DTYPE_F16, sem_in || sem_in16, st);
+        return launch_lp8(p, sem_mode, dtype, save, st);
     }
-    if (sem_in || sem_in16) {
-        NSOS_REQUIRE((sem_in16 ? (void*)sem_hid16 : (void*)sem_hid) && sem_mode != NSOS_SEM_NONE, NSOS_ERR_UNSUPPORTED);
-        if (dtype == NSOS_DTYPE_F16) return sem_mode == 1 ? launch_lp<F16, 1, true>(p, st) : launch_lp<F16, 2, true>(p, st);
-        return sem_mode == 1 ? launch_lp<BF16, 1, true>(p, st) : launch_lp<BF16, 2, true>(p, st);
-    }
-    if (dtype == NSOS_DTYPE_F16) {
-        switch (sem_mode) {
-            case 0: return launch_lp<F16, 0>(p, st);
-            case 1: return launch_lp<F16, 1>(p, st);
-            default: return launch_lp<F16, 2>(p, st);
-        }
-    }
-    switch (sem_mode) {
-        case 0: return launch_lp<BF16, 0>(p, st);
-        case 1: return launch_lp<BF16, 1>(p, st);
-        default: return launch_lp<BF16, 2>(p, st);
-    }
+    return dispatch_lp(sem_mode, dtype, save, [&](auto t, auto sem, auto sv) -> int32_t {
+        return launch_lp<decltype(t), decltype(sem)::value, decltype(sv)::value != 0>(p, st);
+    });
 }
+
+#define NSOS_RAY_CALL NsosRayCall{packed, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw}
 
 extern "C" int32_t nsos_mlp_forward_rays_lp(const void* packed, int32_t sem_mode, int32_t dtype, const float* rays_o,
                                             const float* rays_d, const float* viewdirs, const float* z_vals,
                                             int64_t n_rays, int32_t n_samples, float* raw, void* stream) {
-    return forward_rays_lp(packed, sem_mode, dtype, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw, nullptr, nullptr,
-                           nullptr, stream);
+    return forward_rays_lp(NSOS_RAY_CALL, sem_mode, dtype, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int32_t nsos_mlp_forward_rays_save_lp(const void* packed, int32_t sem_mode, int32_t dtype, const float* rays_o,
@@ -655,10 +618,9 @@ extern "C" int32_t nsos_mlp_forward_rays_save_lp(const void* packed, int32_t sem
                                                  int64_t n_rays, int32_t n_samples, float* raw, float* sem_in,
                                                  float* sem_hid, void* stream) {
     if (n_rays == 0) return NSOS_OK;
-    NSOS_REQUIRE(sem_in && sem_hid, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(((uintptr_t)sem_in & 15) == 0 && ((uintptr_t)sem_hid & 15) == 0, NSOS_ERR_MISALIGNED);
-    return forward_rays_lp(packed, sem_mode, dtype, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw, nullptr, sem_in,
-                           sem_hid, stream);
+    const int32_t rc = nsos_check_outputs({sem_in, sem_hid});
+    if (rc != NSOS_OK) return rc;
+    return forward_rays_lp(NSOS_RAY_CALL, sem_mode, dtype, nullptr, sem_in, sem_hid, stream);
 }
 
 extern "C" int32_t nsos_mlp_save16_layout(int64_t n_points) {   // the same condition forward_rays_lp selects the kernel by
@@ -671,10 +633,10 @@ extern "C" int32_t nsos_mlp_forward_rays_save16_lp(const void* packed, int32_t s
                                                    int64_t n_rays, int32_t n_samples, float* raw, void* sem_in16,
                                                    void* sem_hid16, void* stream) {
     if (n_rays == 0) return NSOS_OK;
-    NSOS_REQUIRE(sem_in16 && sem_hid16, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(((uintptr_t)sem_in16 & 15) == 0 && ((uintptr_t)sem_hid16 & 15) == 0, NSOS_ERR_MISALIGNED);
-    return forward_rays_lp(packed, sem_mode, dtype, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw, nullptr, nullptr,
-                           nullptr, stream, static_cast<unsigned*>(sem_in16), static_cast<unsigned*>(sem_hid16));
+    const int32_t rc = nsos_check_outputs({sem_in16, sem_hid16});
+    if (rc != NSOS_OK) return rc;
+    return forward_rays_lp(NSOS_RAY_CALL, sem_mode, dtype, nullptr, nullptr, nullptr, stream, static_cast<unsigned*>(sem_in16),
+                           static_cast<unsigned*>(sem_hid16));
 }
 
 extern "C" int32_t nsos_mlp_profile_rays_lp(const void* packed, int32_t sem_mode, int32_t dtype, const float* rays_o,
@@ -683,6 +645,5 @@ extern "C" int32_t nsos_mlp_profile_rays_lp(const void* packed, int32_t sem_mode
                                             void* stream) {
     if (n_rays == 0) return NSOS_OK;
     NSOS_REQUIRE(stamps, NSOS_ERR_NULL_POINTER);
-    return forward_rays_lp(packed, sem_mode, dtype, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw,
-                           reinterpret_cast<unsigned long long*>(stamps), nullptr, nullptr, stream);
+    return forward_rays_lp(NSOS_RAY_CALL, sem_mode, dtype, reinterpret_cast<unsigned long long*>(stamps), nullptr, nullptr, stream);
 }

@@ -784,20 +784,9 @@ static_assert(kLdsBytes16 <= 160 * 1024, "LDS");
 
 template <class T, int SEM, bool SAVE, bool PROF>
 int32_t launch16p(const LpParams& p, hipStream_t stream) {
-    static NsosPerDeviceFlag configured_on;
-    bool& configured = configured_on.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_lp16_kernel<T, SEM, SAVE, PROF>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes16);
-        if (e != hipSuccess) return (int32_t)e;
-        configured = true;
-    }
-    const int cus = nsos_device_cus();
-    LpParams q = p;
+    LpParams q = p;   // this kernel's own tile size
     q.n_tiles = (int)((p.n_pts + kTile16 - 1) / kTile16);
-    const int grid = q.n_tiles < cus ? q.n_tiles : cus;
-    hipLaunchKernelGGL((mlp_lp16_kernel<T, SEM, SAVE, PROF>), dim3(grid), dim3(64 * kW16), kLdsBytes16, stream, q);
-    return nsos_launch_status();
+    return nsos_launch_persistent<&mlp_lp16_kernel<T, SEM, SAVE, PROF>>(q, q.n_tiles, 64 * kW16, kLdsBytes16, stream);
 }
 template <class T, int SEM, bool SAVE>
 int32_t launch16(const LpParams& p, hipStream_t stream) {
@@ -976,23 +965,10 @@ int32_t pack_lp16(const void* tensors, int32_t sem_mode, bool is_f16, unsigned c
 }
 
 // dispatch used by forward_rays_lp (mlp_lp.hip); sem_mode and dtype were validated there
-int32_t launch_lp16(const LpParams& p, int32_t sem_mode, bool is_f16, bool save, hipStream_t st) {
-    if (save) {
-        if (is_f16) return sem_mode == 1 ? launch16<F16, 1, true>(p, st) : launch16<F16, 2, true>(p, st);
-        return sem_mode == 1 ? launch16<BF16, 1, true>(p, st) : launch16<BF16, 2, true>(p, st);
-    }
-    if (is_f16) {
-        switch (sem_mode) {
-            case 0: return launch16<F16, 0, false>(p, st);
-            case 1: return launch16<F16, 1, false>(p, st);
-            default: return launch16<F16, 2, false>(p, st);
-        }
-    }
-    switch (sem_mode) {
-        case 0: return launch16<BF16, 0, false>(p, st);
-        case 1: return launch16<BF16, 1, false>(p, st);
-        default: return launch16<BF16, 2, false>(p, st);
-    }
+int32_t launch_lp16(const LpParams& p, int32_t sem_mode, int32_t dtype, bool save, hipStream_t st) {
+    return dispatch_lp(sem_mode, dtype, save, [&](auto t, auto sem, auto sv) -> int32_t {
+        return launch16<decltype(t), decltype(sem)::value, decltype(sv)::value != 0>(p, st);
+    });
 }
 
 }  // namespace lp

@@ -735,18 +735,7 @@ constexpr int kLdsBytes8 = kSlots * kSlotBytes + kAuxWords * 4 + 8 * 768;   // 4
 
 template <class T, int SEM, bool SAVE, bool PROF>
 int32_t launch8p(const LpParams& p, hipStream_t stream) {
-    static NsosPerDeviceFlag configured_on;
-    bool& configured = configured_on.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_lp8_kernel<T, SEM, SAVE, PROF>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes8);
-        if (e != hipSuccess) return (int32_t)e;
-        configured = true;
-    }
-    const int cus = nsos_device_cus();
-    const int grid = p.n_tiles < cus ? p.n_tiles : cus;
-    hipLaunchKernelGGL((mlp_lp8_kernel<T, SEM, SAVE, PROF>), dim3(grid), dim3(512), kLdsBytes8, stream, p);
-    return nsos_launch_status();
+    return nsos_launch_persistent<&mlp_lp8_kernel<T, SEM, SAVE, PROF>>(p, p.n_tiles, 512, kLdsBytes8, stream);
 }
 template <class T, int SEM, bool SAVE>
 int32_t launch8(const LpParams& p, hipStream_t stream) {
@@ -763,23 +752,10 @@ namespace nsos {
 namespace lp {
 
 // dispatch used by forward_rays_lp (mlp_lp.hip); sem_mode and dtype were validated there
-int32_t launch_lp8(const LpParams& p, int32_t sem_mode, bool is_f16, bool save, hipStream_t st) {
-    if (save) {
-        if (is_f16) return sem_mode == 1 ? launch8<F16, 1, true>(p, st) : launch8<F16, 2, true>(p, st);
-        return sem_mode == 1 ? launch8<BF16, 1, true>(p, st) : launch8<BF16, 2, true>(p, st);
-    }
-    if (is_f16) {
-        switch (sem_mode) {
-            case 0: return launch8<F16, 0, false>(p, st);
-            case 1: return launch8<F16, 1, false>(p, st);
-            default: return launch8<F16, 2, false>(p, st);
-        }
-    }
-    switch (sem_mode) {
-        case 0: return launch8<BF16, 0, false>(p, st);
-        case 1: return launch8<BF16, 1, false>(p, st);
-        default: return launch8<BF16, 2, false>(p, st);
-    }
+int32_t launch_lp8(const LpParams& p, int32_t sem_mode, int32_t dtype, bool save, hipStream_t st) {
+    return dispatch_lp(sem_mode, dtype, save, [&](auto t, auto sem, auto sv) -> int32_t {
+        return launch8<decltype(t), decltype(sem)::value, decltype(sv)::value != 0>(p, st);
+    });
 }
 
 }  // namespace lp

@@ -28,6 +28,7 @@
 //     output heads: fp32 VALU on the summed fp32 accumulators.
 // Compiled with -ffp-contract=off (x = o + d*z stays a separately rounded multiply and add).
 #include "x3_common.h"
+#include "mlp_host.h"
 #include "x316.h"
 #include <cstdlib>
 #include <cstring>
@@ -579,22 +580,6 @@ __global__ __launch_bounds__(256) void x3_pack_kernel(const X3PackParams P) {
 
 constexpr int kLdsBytes = kSlots * kSlotBytes + kAuxWords * 4;
 
-template <int SEM, int SAVE = 0>
-int32_t launch_x3(const X3Params& p, hipStream_t stream) {
-    static NsosPerDeviceFlag configured_on;
-    bool& configured = configured_on.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_x3_kernel<SEM, SAVE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        if (e != hipSuccess) return (int32_t)e;
-        configured = true;
-    }
-    const int cus = nsos_device_cus();
-    const int grid = p.n_tiles < cus ? p.n_tiles : cus;
-    hipLaunchKernelGGL((mlp_x3_kernel<SEM, SAVE>), dim3(grid), dim3(256), kLdsBytes, stream, p);
-    return nsos_launch_status();
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ C ABI
@@ -625,14 +610,8 @@ extern "C" int32_t nsos_mlp_x3_select_kernel(int32_t kernel) {
 extern "C" int32_t nsos_mlp_x3_selected_kernel(void) { return x3_kernel(); }
 
 extern "C" int32_t nsos_mlp_pack_x3(const nsos_mlp_tensors* T_, int32_t sem_mode, void* packed, size_t packed_bytes, void* stream) {
-    NSOS_REQUIRE(T_ && packed, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(sem_mode >= 0 && sem_mode <= 2, NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(packed_bytes >= nsos_mlp_packed_bytes_x3(sem_mode), NSOS_ERR_BUFFER_TOO_SMALL);
-    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0, NSOS_ERR_MISALIGNED);
-    for (int l = 0; l < NSOS_NET_DEPTH; ++l) NSOS_REQUIRE(T_->pts_w[l] && T_->pts_b[l], NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(T_->alpha_w && T_->alpha_b && T_->feature_w && T_->feature_b && T_->views_w && T_->views_b &&
-                     T_->rgb_w && T_->rgb_b, NSOS_ERR_NULL_POINTER);
-    if (sem_mode) NSOS_REQUIRE(T_->sem0_w && T_->sem0_b && T_->sem2_w && T_->sem2_b, NSOS_ERR_NULL_POINTER);
+    const int32_t ok = nsos_check_pack(T_, sem_mode, nsos_sem_mode_ok(sem_mode), packed, packed_bytes, nsos_mlp_packed_bytes_x3(sem_mode));
+    if (ok != NSOS_OK) return ok;
 
     X3PackParams P = {};
     int n = 0;
@@ -679,64 +658,54 @@ extern "C" int32_t nsos_mlp_pack_x3(const nsos_mlp_tensors* T_, int32_t sem_mode
 }
 
 namespace {
-int32_t forward_x3(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d, const float* viewdirs,
-                   const float* z_vals, int64_t n_rays, int32_t n_samples, float* raw, float* sem_in, float* sem_hid,
-                   float* acts, int save, void* stream, unsigned long long* prof = nullptr, unsigned* masks = nullptr) {
-    if (n_rays == 0) return NSOS_OK;
-    NSOS_REQUIRE(packed && rays_o && rays_d && viewdirs && z_vals && raw, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(n_rays > 0 && n_samples >= 1, NSOS_ERR_BAD_SHAPE);
-    NSOS_REQUIRE(n_rays < (1ll << 31), NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(sem_mode >= 0 && sem_mode <= 2, NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)raw & 15) == 0, NSOS_ERR_MISALIGNED);
-    if (save == 1) {
+// save: 0 inference (the selected forward kernel), 1 the semantic head's inputs, 2 / 3 every layer's activations as fp32 / fp16 + ReLU masks
+int32_t forward_x3(const NsosRayCall& c, int32_t sem_mode, float* sem_in, float* sem_hid, float* acts, int save, void* stream,
+                   unsigned long long* prof = nullptr, unsigned* masks = nullptr) {
+    if (c.n_rays == 0) return NSOS_OK;
+    int32_t rc = nsos_check_ray_call(c, true, nsos_sem_mode_ok(sem_mode));
+    if (rc == NSOS_OK && save == 1) {
         NSOS_REQUIRE(sem_mode != 0, NSOS_ERR_UNSUPPORTED);
-        NSOS_REQUIRE(sem_in && sem_hid, NSOS_ERR_NULL_POINTER);
-        NSOS_REQUIRE(((uintptr_t)sem_in & 15) == 0 && ((uintptr_t)sem_hid & 15) == 0, NSOS_ERR_MISALIGNED);
+        rc = nsos_check_outputs({sem_in, sem_hid});
     }
-    if (save >= 2) {
-        NSOS_REQUIRE(acts && masks, NSOS_ERR_NULL_POINTER);
-        NSOS_REQUIRE(((uintptr_t)acts & 15) == 0 && ((uintptr_t)masks & 15) == 0, NSOS_ERR_MISALIGNED);
-    }
-    const long long n_pts = (long long)n_rays * n_samples;
-    NSOS_REQUIRE((n_pts + kTilePts - 1) / kTilePts < (1ll << 31), NSOS_ERR_UNSUPPORTED);
-    if (save == 0 && x3_kernel() == 2)          // inference: the 16x16x32 kernel on its own stream behind the first one
-        return nsos::x316::launch(static_cast<const unsigned char*>(packed) + x3_first_stream_bytes(sem_mode), sem_mode, rays_o, rays_d, viewdirs,
-                                  z_vals, n_pts, n_samples, raw, prof, (hipStream_t)stream);
-    X3Params p = {};
-    p.aux = static_cast<const unsigned*>(packed);
-    p.chunks = reinterpret_cast<const unsigned char*>(p.aux + kAuxWords);
-    p.rays_o = rays_o; p.rays_d = rays_d; p.viewdirs = viewdirs; p.z_vals = z_vals;
-    p.raw = raw; p.n_pts = n_pts; p.n_samples = n_samples;
-    p.n_tiles = (int)((n_pts + kTilePts - 1) / kTilePts);
-    p.sem_in = sem_in; p.sem_hid = sem_hid; p.acts = acts; p.prof = prof; p.masks = masks;
+    if (rc == NSOS_OK && save >= 2) rc = nsos_check_outputs({acts, masks});
+    if (rc != NSOS_OK) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    if (save == 1) return sem_mode == 1 ? launch_x3<1, 1>(p, st) : launch_x3<2, 1>(p, st);
-    if (save == 2) return sem_mode == 0 ? launch_x3<0, 2>(p, st) : (sem_mode == 1 ? launch_x3<1, 2>(p, st) : launch_x3<2, 2>(p, st));
-    if (save == 3) return sem_mode == 0 ? launch_x3<0, 3>(p, st) : (sem_mode == 1 ? launch_x3<1, 3>(p, st) : launch_x3<2, 3>(p, st));
-    switch (sem_mode) {
-        case 0: return launch_x3<0>(p, st);
-        case 1: return launch_x3<1>(p, st);
-        default: return launch_x3<2>(p, st);
-    }
+    if (save == 0 && x3_kernel() == 2)          // inference: the 16x16x32 kernel on its own stream behind the first one
+        return nsos::x316::launch(static_cast<const unsigned char*>(c.packed) + x3_first_stream_bytes(sem_mode), sem_mode, c, prof, st);
+    X3Params p = {};
+    rc = nsos_fill_ray_call(p, c, kTilePts);
+    if (rc != NSOS_OK) return rc;
+    p.aux = static_cast<const unsigned*>(c.packed);
+    p.chunks = reinterpret_cast<const unsigned char*>(p.aux + kAuxWords);
+    p.sem_in = sem_in; p.sem_hid = sem_hid; p.acts = acts; p.prof = prof; p.masks = masks;
+    return nsos_dispatch_sem(sem_mode, [&](auto sem) -> int32_t {
+        return nsos_dispatch_below<4>(save, [&](auto sv) -> int32_t {
+            constexpr int SEM = decltype(sem)::value, SAVE = decltype(sv)::value;
+            if constexpr (SEM == 0 && SAVE == 1) return NSOS_ERR_UNSUPPORTED;
+            else return nsos_launch_persistent<&mlp_x3_kernel<SEM, SAVE>>(p, p.n_tiles, 256, kLdsBytes, st);
+        });
+    });
 }
 }  // namespace
+
+#define NSOS_RAY_CALL NsosRayCall{packed, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw}
 
 extern "C" int32_t nsos_mlp_forward_rays_x3(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
                                             const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples,
                                             float* raw, void* stream) {
-    return forward_x3(packed, sem_mode, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw, nullptr, nullptr, nullptr, 0, stream);
+    return forward_x3(NSOS_RAY_CALL, sem_mode, nullptr, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int32_t nsos_mlp_forward_rays_save_x3(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
                                                  const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples,
                                                  float* raw, float* sem_in, float* sem_hid, void* stream) {
-    return forward_x3(packed, sem_mode, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw, sem_in, sem_hid, nullptr, 1, stream);
+    return forward_x3(NSOS_RAY_CALL, sem_mode, sem_in, sem_hid, nullptr, 1, stream);
 }
 
 extern "C" int32_t nsos_mlp_forward_rays_save_all_x3(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
                                                      const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples,
                                                      float* raw, float* acts, void* relu_masks, void* stream) {
-    return forward_x3(packed, sem_mode, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw, nullptr, nullptr, acts, 2, stream,
+    return forward_x3(NSOS_RAY_CALL, sem_mode, nullptr, nullptr, acts, 2, stream,
                       nullptr, static_cast<unsigned*>(relu_masks));
 }
 
@@ -745,7 +714,7 @@ extern "C" int32_t nsos_mlp_forward_rays_save_all_x3(const void* packed, int32_t
 extern "C" int32_t nsos_mlp_forward_rays_save_all16_x3(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,
                                                        const float* viewdirs, const float* z_vals, int64_t n_rays, int32_t n_samples,
                                                        float* raw, void* acts_f16, void* relu_masks, void* stream) {
-    return forward_x3(packed, sem_mode, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw, nullptr, nullptr,
+    return forward_x3(NSOS_RAY_CALL, sem_mode, nullptr, nullptr,
                       static_cast<float*>(acts_f16), 3, stream, nullptr, static_cast<unsigned*>(relu_masks));
 }
 
@@ -758,6 +727,6 @@ extern "C" int32_t nsos_mlp_profile_rays_x3(const void* packed, int32_t sem_mode
                                             float* raw, uint64_t* stamps, void* stream) {
     if (n_rays == 0) return NSOS_OK;
     NSOS_REQUIRE(stamps, NSOS_ERR_NULL_POINTER);
-    return forward_x3(packed, sem_mode, rays_o, rays_d, viewdirs, z_vals, n_rays, n_samples, raw, nullptr, nullptr, nullptr, 0, stream,
+    return forward_x3(NSOS_RAY_CALL, sem_mode, nullptr, nullptr, nullptr, 0, stream,
                       reinterpret_cast<unsigned long long*>(stamps));
 }

@@ -619,27 +619,11 @@ __global__ __launch_bounds__(64 * kW16, 1) void mlp_x316_kernel(const X316Params
     __syncthreads();
 }
 
-template <int SEM, bool PROF>
-int32_t launch_x316p(const X316Params& p, hipStream_t stream) {
-    static NsosPerDeviceFlag configured_on;
-    bool& configured = configured_on.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_x316_kernel<SEM, PROF>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesX);
-        if (e != hipSuccess) return (int32_t)e;
-        configured = true;
-    }
-    const int cus = nsos_device_cus();
-    X316Params q = p;
-    q.n_tiles = (int)((p.n_pts + kTileX - 1) / kTileX);
-    const int grid = q.n_tiles < cus ? q.n_tiles : cus;
-    hipLaunchKernelGGL((mlp_x316_kernel<SEM, PROF>), dim3(grid), dim3(64 * kW16), kLdsBytesX, stream, q);
-    return nsos_launch_status();
-}
 template <int SEM>
 int32_t launch_x316s(const X316Params& p, hipStream_t stream) {
-    if (p.prof) return launch_x316p<SEM, true>(p, stream);
-    return launch_x316p<SEM, false>(p, stream);
+    return nsos_dispatch_bool(p.prof != nullptr, [&](auto prof) -> int32_t {
+        return nsos_launch_persistent<&mlp_x316_kernel<SEM, decltype(prof)::value != 0>>(p, p.n_tiles, 64 * kW16, kLdsBytesX, stream);
+    });
 }
 
 // ------------------------------------------------------------------------------------------ packing
@@ -791,17 +775,13 @@ int32_t pack(const void* tensors, int32_t sem_mode, unsigned char* chunks, hipSt
     return nsos_launch_status();
 }
 
-int32_t launch(const unsigned char* chunks, int32_t sem_mode, const float* rays_o, const float* rays_d, const float* viewdirs,
-               const float* z_vals, long long n_pts, int32_t n_samples, float* raw, unsigned long long* prof, hipStream_t stream) {
+int32_t launch(const unsigned char* chunks, int32_t sem_mode, const NsosRayCall& c, unsigned long long* prof, hipStream_t stream) {
     X316Params p = {};
+    const int32_t rc = nsos_fill_ray_call(p, c, kTileX);
+    if (rc != NSOS_OK) return rc;
     p.chunks = chunks;
-    p.rays_o = rays_o; p.rays_d = rays_d; p.viewdirs = viewdirs; p.z_vals = z_vals;
-    p.raw = raw; p.n_pts = n_pts; p.n_samples = n_samples; p.prof = prof;
-    switch (sem_mode) {
-        case 0: return launch_x316s<0>(p, stream);
-        case 1: return launch_x316s<1>(p, stream);
-        default: return launch_x316s<2>(p, stream);
-    }
+    p.prof = prof;
+    return nsos_dispatch_sem(sem_mode, [&](auto sem) -> int32_t { return launch_x316s<decltype(sem)::value>(p, stream); });
 }
 
 }  // namespace x316

@@ -22,6 +22,7 @@
 // to a sum it contributes 1e-3 of).  The caller divides the weight gradients by the scale their gbuf block carries.
 // Products: g_hi.W_hi + g_lo.W_hi + g_hi.(2^11 W_lo), fp32 accumulation, as in the forward kernel.
 #include "x3_common.h"
+#include "mlp_host.h"
 
 typedef unsigned u32x2_b __attribute__((ext_vector_type(2)));
 namespace {
@@ -312,18 +313,7 @@ constexpr int kLdsBytes = kSlots * kSlotBytes + kBAuxWords * 4;
 
 template <int SEM, bool BITS, bool A16 = false>
 int32_t launch_x3_bwd(const X3BwdParams& p, hipStream_t stream) {
-    static NsosPerDeviceFlag configured_on;
-    bool& configured = configured_on.here();
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_x3_bwd_kernel<SEM, BITS, A16>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        if (e != hipSuccess) return (int32_t)e;
-        configured = true;
-    }
-    const int cus = nsos_device_cus();
-    const int grid = p.n_tiles < cus ? p.n_tiles : cus;
-    hipLaunchKernelGGL((mlp_x3_bwd_kernel<SEM, BITS, A16>), dim3(grid), dim3(256), kLdsBytes, stream, p);
-    return nsos_launch_status();
+    return nsos_launch_persistent<&mlp_x3_bwd_kernel<SEM, BITS, A16>>(p, p.n_tiles, 256, kLdsBytes, stream);
 }
 
 }  // namespace
@@ -335,13 +325,9 @@ extern "C" size_t nsos_mlp_bwd_packed_bytes_x3(int32_t sem_mode) {
 }
 
 extern "C" int32_t nsos_mlp_bwd_pack_x3(const nsos_mlp_tensors* T_, int32_t sem_mode, void* packed, size_t packed_bytes, void* stream) {
-    NSOS_REQUIRE(T_ && packed, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(sem_mode >= 0 && sem_mode <= 2, NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(packed_bytes >= nsos_mlp_bwd_packed_bytes_x3(sem_mode), NSOS_ERR_BUFFER_TOO_SMALL);
-    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0, NSOS_ERR_MISALIGNED);
-    for (int l = 1; l < NSOS_NET_DEPTH; ++l) NSOS_REQUIRE(T_->pts_w[l], NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(T_->alpha_w && T_->feature_w && T_->views_w && T_->rgb_w, NSOS_ERR_NULL_POINTER);
-    if (sem_mode) NSOS_REQUIRE(T_->sem0_w && T_->sem2_w, NSOS_ERR_NULL_POINTER);
+    const int32_t ok = nsos_check_pack(T_, sem_mode, nsos_sem_mode_ok(sem_mode), packed, packed_bytes, nsos_mlp_bwd_packed_bytes_x3(sem_mode),
+                                       /*with_biases=*/false);
+    if (ok != NSOS_OK) return ok;
 
     X3BwdPackParams P = {};
     int n = 0;
@@ -368,23 +354,23 @@ static int32_t input_grads_x3(const void* packed, int32_t sem_mode, const float*
     if (n_pts == 0) return NSOS_OK;
     NSOS_REQUIRE(packed && g_raw && acts && scale && gbuf, NSOS_ERR_NULL_POINTER);
     NSOS_REQUIRE(n_pts > 0, NSOS_ERR_BAD_SHAPE);
-    NSOS_REQUIRE(sem_mode >= 0 && sem_mode <= 2, NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)acts & 15) == 0 && ((uintptr_t)gbuf & 15) == 0, NSOS_ERR_MISALIGNED);
-    NSOS_REQUIRE((n_pts + kTilePts - 1) / kTilePts < (1ll << 31), NSOS_ERR_UNSUPPORTED);
+    NSOS_REQUIRE(nsos_sem_mode_ok(sem_mode), NSOS_ERR_UNSUPPORTED);
+    NSOS_REQUIRE(nsos_aligned16({packed, acts, gbuf}), NSOS_ERR_MISALIGNED);
     X3BwdParams p = {};
+    const int32_t rc = nsos_fill_points(p, n_pts, kTilePts);
+    if (rc != NSOS_OK) return rc;
+    NSOS_REQUIRE(nsos_aligned16({relu_masks}), NSOS_ERR_MISALIGNED);
+    if (acts16) NSOS_REQUIRE(relu_masks, NSOS_ERR_NULL_POINTER);      // 16-bit activations carry no usable trunk masks of their own
     p.aux = static_cast<const unsigned*>(packed);
     p.chunks = reinterpret_cast<const unsigned char*>(p.aux + kBAuxWords);
-    NSOS_REQUIRE(((uintptr_t)relu_masks & 15) == 0, NSOS_ERR_MISALIGNED);
     p.g_raw = g_raw; p.acts = acts; p.gbuf = gbuf; p.scale = scale; p.masks = static_cast<const unsigned*>(relu_masks);
-    p.n_pts = n_pts;
-    p.n_tiles = (int)((n_pts + kTilePts - 1) / kTilePts);
     const hipStream_t st = (hipStream_t)stream;
-    if (acts16) {
-        NSOS_REQUIRE(relu_masks, NSOS_ERR_NULL_POINTER);      // 16-bit activations carry no usable trunk masks of their own
-        return sem_mode == 0 ? launch_x3_bwd<0, true, true>(p, st) : launch_x3_bwd<1, true, true>(p, st);
-    }
-    if (relu_masks) return sem_mode == 0 ? launch_x3_bwd<0, true>(p, st) : launch_x3_bwd<1, true>(p, st);
-    return sem_mode == 0 ? launch_x3_bwd<0, false>(p, st) : launch_x3_bwd<1, false>(p, st);
+    return nsos_dispatch_bool(sem_mode != NSOS_SEM_NONE, [&](auto sem) -> int32_t {   // the chain is the same with and without the coordinates
+        constexpr int SEM = decltype(sem)::value;
+        if (acts16) return launch_x3_bwd<SEM, true, true>(p, st);
+        if (relu_masks) return launch_x3_bwd<SEM, true>(p, st);
+        return launch_x3_bwd<SEM, false>(p, st);
+    });
 }
 
 extern "C" int32_t nsos_mlp_input_grads_x3(const void* packed, int32_t sem_mode, const float* g_raw, const float* acts,

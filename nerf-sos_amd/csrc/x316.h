@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
+#include "mlp_host.h"
+
 namespace nsos {
 namespace x316 {
 
@@ -18,8 +20,8 @@ constexpr size_t kX316SlotBytes = 36 * 1024;
 __host__ __device__ constexpr size_t stream_bytes(int sem) { return (size_t)x316_chunks(sem) * kX316SlotBytes + kX316TailBytes; }
 
 int32_t pack(const void* tensors, int32_t sem_mode, unsigned char* chunks, hipStream_t stream);
-int32_t launch(const unsigned char* chunks, int32_t sem_mode, const float* rays_o, const float* rays_d, const float* viewdirs,
-               const float* z_vals, long long n_pts, int32_t n_samples, float* raw, unsigned long long* prof, hipStream_t stream);
+// `call` has passed nsos_check_ray_call; refuses a launch of 2^31 tiles or more
+int32_t launch(const unsigned char* chunks, int32_t sem_mode, const NsosRayCall& call, unsigned long long* prof, hipStream_t stream);
 
 }  // namespace x316
 }  // namespace nsos

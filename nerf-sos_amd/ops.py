@@ -48,6 +48,17 @@ def _dev(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def _rays(rays_o, rays_d, viewdirs, z_vals, viewdirs_optional: bool = False):
+    """The ray wrappers' preamble: the four inputs as contiguous fp32 GPU tensors (viewdirs_optional: None stays None, for nets
+    without a view branch), then R, S and the device."""
+    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
+    if viewdirs is not None or not viewdirs_optional:
+        viewdirs = _dev(viewdirs, "viewdirs")
+    z_vals = _dev(z_vals, "z_vals")
+    R, S = z_vals.shape
+    return rays_o, rays_d, viewdirs, z_vals, R, S, z_vals.device
+
+
 def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -365,11 +376,8 @@ INPUT_GRADS_BIT = 1 << 31      # OR-ed into a trainable mask: "the backward also
 def mlp_generic_forward_rays(plan: GenericPlan, packed: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor,
                              viewdirs: Optional[torch.Tensor], z_vals: torch.Tensor) -> torch.Tensor:
     """raw [R,S,C] for the points o + d*z of each ray through the generic-architecture kernel (models/nerf_mlp.py:67-100,179-215)."""
-    rays_o, rays_d, z_vals = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d"), _dev(z_vals, "z_vals")
-    if viewdirs is not None:
-        viewdirs = _dev(viewdirs, "viewdirs")
-    R, S = z_vals.shape
-    raw = torch.empty((R, S, plan.out_channels), device=z_vals.device, dtype=torch.float32)
+    rays_o, rays_d, viewdirs, z_vals, R, S, dev = _rays(rays_o, rays_d, viewdirs, z_vals, viewdirs_optional=True)
+    raw = torch.empty((R, S, plan.out_channels), device=dev, dtype=torch.float32)
     ev = _ev_begin()
     _lib.check(_lib.lib().nsos_mlp_generic_forward_rays(C.byref(plan.desc), _p(packed), _p(rays_o), _p(rays_d), _p(viewdirs), _p(z_vals),
                                                         R, S, _p(raw), _stream()), "nsos_mlp_generic_forward_rays")
@@ -381,13 +389,10 @@ def mlp_generic_forward_rays_save(plan: GenericPlan, packed: torch.Tensor, rays_
                                   viewdirs: Optional[torch.Tensor], z_vals: torch.Tensor, trainable: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Training variant of mlp_generic_forward_rays: also returns acts [R*S, ld], every Linear's post-activation output and both
     encodings per point (nsos_mlp_generic_forward_rays_save; raw is bit-identical to the inference call's)."""
-    rays_o, rays_d, z_vals = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d"), _dev(z_vals, "z_vals")
-    if viewdirs is not None:
-        viewdirs = _dev(viewdirs, "viewdirs")
-    R, S = z_vals.shape
+    rays_o, rays_d, viewdirs, z_vals, R, S, dev = _rays(rays_o, rays_d, viewdirs, z_vals, viewdirs_optional=True)
     ld = plan.layout()[0]
-    raw = torch.empty((R, S, plan.out_channels), device=z_vals.device, dtype=torch.float32)
-    acts = torch.empty((R * S, ld), device=z_vals.device, dtype=torch.float32)
+    raw = torch.empty((R, S, plan.out_channels), device=dev, dtype=torch.float32)
+    acts = torch.empty((R * S, ld), device=dev, dtype=torch.float32)
     if trainable is not None:      # a GenericPlan.trainable_mask(): store only what that subset's backward reads
         _lib.check(_lib.lib().nsos_mlp_generic_forward_rays_save_subset(C.byref(plan.desc), _p(packed), _p(rays_o), _p(rays_d), _p(viewdirs), _p(z_vals),
                                                                         R, S, _p(raw), _p(acts), int(trainable), _stream()),
@@ -411,18 +416,16 @@ def mlp_generic_input_grads(plan: GenericPlan, packed_bwd: torch.Tensor, g_raw: 
         _lib.check(_lib.lib().nsos_mlp_generic_input_grads(C.byref(plan.desc), _p(packed_bwd), _p(g_raw), _p(acts), _p(gbuf), P_, _stream()),
                    "nsos_mlp_generic_input_grads")
         return gbuf
-    rays_o, rays_d, viewdirs, z_vals = rays
-    rays_o, rays_d, z_vals = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d"), _dev(z_vals, "z_vals")
-    R, S = z_vals.shape
+    use_viewdirs = bool(plan.desc.use_viewdirs)    # a net without a view branch ignores whatever viewdirs holds
+    rays_o, rays_d, viewdirs, z_vals, R, S, _ = _rays(rays[0], rays[1], rays[2] if use_viewdirs else None, rays[3], viewdirs_optional=not use_viewdirs)
     if R * S != P_:
         raise ValueError("mlp_generic_input_grads: rays do not match the saved activations")
     g_pts = torch.empty((P_, 3), device=acts.device, dtype=torch.float32)
     g_dirs = None
-    if plan.desc.use_viewdirs:
-        viewdirs = _dev(viewdirs, "viewdirs")
+    if use_viewdirs:
         g_dirs = torch.empty((P_, 3), device=acts.device, dtype=torch.float32)
     _lib.check(_lib.lib().nsos_mlp_generic_input_grads_rays(C.byref(plan.desc), _p(packed_bwd), _p(g_raw), _p(acts), _p(gbuf), _p(rays_o), _p(rays_d),
-                                                            _p(viewdirs) if g_dirs is not None else None, _p(z_vals), R, S, _p(g_pts), _p(g_dirs), _stream()),
+                                                            _p(viewdirs), _p(z_vals), R, S, _p(g_pts), _p(g_dirs), _stream()),
                "nsos_mlp_generic_input_grads_rays")
     return gbuf, g_pts, g_dirs
 
@@ -508,21 +511,14 @@ def mlp_forward_rays(packed: torch.Tensor, sem_mode: int, rays_o: torch.Tensor, 
     """raw [R,S,C] for the points o + d*z of each ray  (models/nerf_mlp.py:67-100,179-215).
     fold: `packed` is the folded stream (pack_mlp(..., precision="fp32_fold")): feature_linear multiplied into views_linears.0
     at pack time, 11 % fewer MFMAs; sigma / semantics bit-identical to the unfolded kernel, rgb equal up to rounding."""
-    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
-    viewdirs, z_vals = _dev(viewdirs, "viewdirs"), _dev(z_vals, "z_vals")
-    R, S = z_vals.shape
+    rays_o, rays_d, viewdirs, z_vals, R, S, dev = _rays(rays_o, rays_d, viewdirs, z_vals)
     Cn = 4 if sem_mode == SEM_NONE else 6
-    raw = torch.empty((R, S, Cn), device=z_vals.device, dtype=torch.float32)
-    ev = None
-    if KERNEL_EVENTS is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
+    raw = torch.empty((R, S, Cn), device=dev, dtype=torch.float32)
+    ev = _ev_begin()
     fn = _lib.lib().nsos_mlp_forward_rays_fold if fold else _lib.lib().nsos_mlp_forward_rays
     _lib.check(fn(_p(_fold_checked(packed, sem_mode, fold)), sem_mode, _p(rays_o), _p(rays_d), _p(viewdirs),
                   _p(z_vals), R, S, _p(raw), _stream()), "nsos_mlp_forward_rays_fold" if fold else "nsos_mlp_forward_rays")
-    if ev is not None:
-        ev[1].record()
-        KERNEL_EVENTS.append((R * S, ev[0], ev[1]))
+    _ev_end(ev, R * S)
     return raw
 
 
@@ -542,11 +538,9 @@ def mlp_profile_rays(packed: torch.Tensor, sem_mode: int, rays_o: torch.Tensor, 
                      z_vals: torch.Tensor, fold: bool = False):
     """Diagnostics: mlp_forward_rays plus the per-phase shader-clock stamps of the first tile of workgroups 0..3
     (nsos_mlp_profile_rays[_fold]): (raw [R,S,C], stamps int64 [16 waves, 64 slots]); slot meaning: scripts/phase_profile.py."""
-    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
-    viewdirs, z_vals = _dev(viewdirs, "viewdirs"), _dev(z_vals, "z_vals")
-    R, S = z_vals.shape
-    raw = torch.empty((R, S, 4 if sem_mode == SEM_NONE else 6), device=z_vals.device, dtype=torch.float32)
-    stamps = torch.zeros((16, 64), device=z_vals.device, dtype=torch.int64)
+    rays_o, rays_d, viewdirs, z_vals, R, S, dev = _rays(rays_o, rays_d, viewdirs, z_vals)
+    raw = torch.empty((R, S, 4 if sem_mode == SEM_NONE else 6), device=dev, dtype=torch.float32)
+    stamps = torch.zeros((16, 64), device=dev, dtype=torch.int64)
     fn = _lib.lib().nsos_mlp_profile_rays_fold if fold else _lib.lib().nsos_mlp_profile_rays
     _lib.check(fn(_p(_fold_checked(packed, sem_mode, fold)), sem_mode, _p(rays_o), _p(rays_d), _p(viewdirs), _p(z_vals), R, S, _p(raw),
                   _p(stamps), _stream()), "nsos_mlp_profile_rays_fold" if fold else "nsos_mlp_profile_rays")
@@ -563,15 +557,10 @@ def mlp_forward_rays_lp(packed: torch.Tensor, sem_mode: int, precision: str, ray
     """K2 on the 16-bit matrix pipe: raw [R,S,C] fp32.  precision "fp16" / "bf16": reduced-precision MFMA inputs with
     fp32 accumulation; "fp16x3": split-fp16 operands, three MFMAs per product, fp32-grade results.  `packed` must
     come from pack_mlp(..., precision=precision)."""
-    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
-    viewdirs, z_vals = _dev(viewdirs, "viewdirs"), _dev(z_vals, "z_vals")
-    R, S = z_vals.shape
+    rays_o, rays_d, viewdirs, z_vals, R, S, dev = _rays(rays_o, rays_d, viewdirs, z_vals)
     Cn = 4 if sem_mode == SEM_NONE else 6
-    raw = torch.empty((R, S, Cn), device=z_vals.device, dtype=torch.float32)
-    ev = None
-    if KERNEL_EVENTS is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
+    raw = torch.empty((R, S, Cn), device=dev, dtype=torch.float32)
+    ev = _ev_begin()
     if precision == "fp16x3":
         _lib.check(_lib.lib().nsos_mlp_forward_rays_x3(_p(packed), sem_mode, _p(rays_o), _p(rays_d), _p(viewdirs),
                                                        _p(z_vals), R, S, _p(raw), _stream()), "nsos_mlp_forward_rays_x3")
@@ -580,9 +569,7 @@ def mlp_forward_rays_lp(packed: torch.Tensor, sem_mode: int, precision: str, ray
         _lib.check(_lib.lib().nsos_mlp_forward_rays_lp(_p(packed), sem_mode, DTYPES[precision], _p(rays_o), _p(rays_d),
                                                        _p(viewdirs), _p(z_vals), R, S, _p(raw), _stream()),
                    "nsos_mlp_forward_rays_lp")
-    if ev is not None:
-        ev[1].record()
-        KERNEL_EVENTS.append((R * S, ev[0], ev[1]))
+    _ev_end(ev, R * S)
     return raw
 
 
@@ -598,10 +585,7 @@ def mlp_forward_rays_save(packed: torch.Tensor, sem_mode: int, rays_o: torch.Ten
         raise NotImplementedError("the folded stream exists for the exact fp32 kernel only")
     if sem_mode == SEM_NONE:
         raise ValueError("mlp_forward_rays_save needs a semantic head")
-    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
-    viewdirs, z_vals = _dev(viewdirs, "viewdirs"), _dev(z_vals, "z_vals")
-    R, S = z_vals.shape
-    dev = z_vals.device
+    rays_o, rays_d, viewdirs, z_vals, R, S, dev = _rays(rays_o, rays_d, viewdirs, z_vals)
     raw = torch.empty((R, S, 6), device=dev, dtype=torch.float32)
     compact = compact and precision in ("fp16", "bf16")
     layout = int(_lib.lib().nsos_mlp_save16_layout(R * S)) if compact else 0
@@ -1071,10 +1055,7 @@ def mlp_forward_rays_save_all(packed: torch.Tensor, sem_mode: int, rays_o: torch
         raise NotImplementedError("the folded stream exists for the exact fp32 kernel only")
     if precision not in ("fp32", "fp16x3"):
         raise NotImplementedError("the full backward needs fp32-accurate activations: precision 'fp32' or 'fp16x3'")
-    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
-    viewdirs, z_vals = _dev(viewdirs, "viewdirs"), _dev(z_vals, "z_vals")
-    R, S = z_vals.shape
-    dev = z_vals.device
+    rays_o, rays_d, viewdirs, z_vals, R, S, dev = _rays(rays_o, rays_d, viewdirs, z_vals)
     raw = torch.empty((R, S, 4 if sem_mode == SEM_NONE else 6), device=dev, dtype=torch.float32)
     if acts16 and precision != "fp16x3":
         raise NotImplementedError("16-bit saved activations exist for the split-fp16 kernels (precision 'fp16x3')")

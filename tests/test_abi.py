@@ -241,3 +241,306 @@ def test_loss_entry_points_refuse_out_of_range_shapes_and_write_nothing():
     assert lib.nsos_geo_correlation_loss(arg, arg, arg, arg, arg, 1, 4, 32, 128, 0.5, 1, 3, 1, 15, 1, L, None, arg, 32, None) == -4
     assert lib.nsos_app_correlation_loss(arg, arg, arg, arg, arg, 1, 7, 5, 3, 1, 13, 20, 32, 0.18, 1, 0.46, 1, L, None, arg, 32, None) == -4
     assert loss[0] == 1234.5
+
+
+# ---- refusals of the shipped-architecture MLP entry points -----------------------------------------------------------
+# Argument names in ABI order (the trailing `stream` left out).  Every case below is refused on the host: no call reaches a launch.
+_RAY = ("packed", "sem_mode", "rays_o", "rays_d", "viewdirs", "z_vals", "n_rays", "n_samples", "raw")
+_RAY_LP = ("packed", "sem_mode", "dtype") + _RAY[2:]
+_PACK = ("T", "sem_mode", "packed", "packed_bytes")
+_PACK_LP = ("T", "sem_mode", "dtype", "packed", "packed_bytes")
+_POINTS = ("packed", "sem_mode", "pts", "dirs", "n_pts", "raw")
+_GRADS = ("packed", "sem_mode", "g_raw", "acts", "relu_masks", "n_pts", "scale", "gbuf")
+_MLP_ENTRIES = {
+    "nsos_mlp_pack": _PACK, "nsos_mlp_pack_fold": _PACK, "nsos_mlp_pack_x3": _PACK, "nsos_mlp_bwd_pack_x3": _PACK,
+    "nsos_mlp_pack_lp": _PACK_LP, "nsos_mlp_pack_lp_heads": _PACK_LP,
+    "nsos_mlp_forward_rays": _RAY, "nsos_mlp_forward_rays_fold": _RAY,
+    "nsos_mlp_forward_rays_save": _RAY + ("sem_in", "sem_hid"), "nsos_mlp_forward_rays_save_fold": _RAY + ("sem_in", "sem_hid"),
+    "nsos_mlp_forward_rays_save_all": _RAY + ("acts",), "nsos_mlp_forward_rays_save_all_fold": _RAY + ("acts",),
+    "nsos_mlp_forward_rays_lp": _RAY_LP, "nsos_mlp_forward_rays_save_lp": _RAY_LP + ("sem_in", "sem_hid"),
+    "nsos_mlp_forward_rays_save16_lp": _RAY_LP + ("sem_in16", "sem_hid16"),
+    "nsos_mlp_forward_rays_x3": _RAY, "nsos_mlp_forward_rays_save_x3": _RAY + ("sem_in", "sem_hid"),
+    "nsos_mlp_forward_rays_save_all_x3": _RAY + ("acts", "relu_masks"), "nsos_mlp_forward_rays_save_all16_x3": _RAY + ("acts", "relu_masks"),
+    "nsos_mlp_profile_rays": _RAY + ("stamps",), "nsos_mlp_profile_rays_fold": _RAY + ("stamps",),
+    "nsos_mlp_profile_rays_lp": _RAY_LP + ("stamps",), "nsos_mlp_profile_rays_x3": _RAY + ("stamps",),
+    "nsos_mlp_forward_points": _POINTS, "nsos_mlp_forward_points_fold": _POINTS,
+    "nsos_mlp_input_grads_x3": _GRADS, "nsos_mlp_input_grads_x3_a16": _GRADS,
+}
+_SCALARS = ("sem_mode", "dtype", "n_rays", "n_samples", "n_pts", "packed_bytes")
+_ALIGNED = ("packed", "raw", "gbuf", "sem_in", "sem_hid", "sem_in16", "sem_hid16", "acts", "relu_masks")   # refused unless 16-byte aligned
+_NEEDS_SEM_HEAD = ("nsos_mlp_forward_rays_save", "nsos_mlp_forward_rays_save_fold", "nsos_mlp_forward_rays_save_lp",
+                   "nsos_mlp_forward_rays_save16_lp", "nsos_mlp_forward_rays_save_x3", "nsos_mlp_pack_lp_heads")
+_PACKED_BYTES = {"nsos_mlp_pack": "nsos_mlp_packed_bytes", "nsos_mlp_pack_fold": "nsos_mlp_packed_bytes_fold",
+                 "nsos_mlp_pack_x3": "nsos_mlp_packed_bytes_x3", "nsos_mlp_bwd_pack_x3": "nsos_mlp_bwd_packed_bytes_x3",
+                 "nsos_mlp_pack_lp": "nsos_mlp_packed_bytes_lp", "nsos_mlp_pack_lp_heads": "nsos_mlp_packed_bytes_lp"}
+_WEIGHTS = [f"pts_w{l}" for l in range(8)] + ["alpha_w", "feature_w", "views_w", "rgb_w", "sem0_w", "sem2_w"]
+_BIASES = [f"pts_b{l}" for l in range(8)] + ["alpha_b", "feature_b", "views_b", "rgb_b", "sem0_b", "sem2_b"]
+# two refusals in one call: the pair's name is "<first> + <second>", each a single case of the entry point
+_PAIRS = [("null:raw", "sem_mode:3"), ("misaligned:raw", "n_rays:2^31"), ("sem_mode:3", "misaligned:packed"), ("n_samples:0", "null:rays_o"),
+          ("dtype:3", "n_samples:0"), ("dtype:3", "misaligned:raw"), ("dtype:3", "n_rays:2^31"), ("null:sem_in", "misaligned:packed"),
+          ("null:sem_hid", "n_samples:0"), ("sem_mode:0", "null:sem_in"), ("sem_mode:0", "misaligned:sem_hid"), ("sem_mode:0", "misaligned:raw"),
+          ("sem_mode:3", "misaligned:sem_in"), ("null:acts", "sem_mode:3"), ("misaligned:acts", "null:raw"), ("misaligned:acts", "n_samples:0"),
+          ("null:relu_masks", "misaligned:raw"), ("misaligned:relu_masks", "tiles:2^31"), ("null:stamps", "null:packed"),
+          ("null:stamps", "sem_mode:3"), ("null:sem_in16", "dtype:3"), ("misaligned:sem_hid16", "null:z_vals"),
+          ("tiles:2^31", "misaligned:raw"), ("tiles:2^31", "sem_mode:3"), ("n_rays:2^31", "sem_mode:3"), ("n_rays:-1", "null:packed"),
+          ("n_rays:-1", "misaligned:packed"), ("n_pts:2^39", "misaligned:raw"), ("n_pts:2^39", "misaligned:gbuf"), ("n_pts:-1", "null:raw"),
+          ("n_pts:-1", "sem_mode:3"), ("sem_mode:3", "n_pts:2^39"), ("sem_mode:3", "misaligned:acts"), ("null:T", "sem_mode:3"),
+          ("sem_mode:3", "packed_bytes:short"), ("packed_bytes:short", "misaligned:packed"), ("misaligned:packed", "null:T.rgb_w"),
+          ("dtype:3", "packed_bytes:short"), ("dtype:0", "null:packed"), ("sem_mode:0", "null:T"), ("sem_mode:0", "packed_bytes:short"),
+          ("packed_bytes:short", "null:T.pts_w3")]
+
+
+def _mlp_refusal_cases(lib, name):
+    """{case: {argument: value}}: what to change in an otherwise valid call of `name` (sem+coord net, fp16, 4 rays x 64 samples)."""
+    args = _MLP_ENTRIES[name]
+    ptrs = [a for a in args if a not in _SCALARS and a != "T"]
+    optional = ["relu_masks"] if name == "nsos_mlp_input_grads_x3" else []
+    count = "n_rays" if "n_rays" in args else "n_pts"
+    cases = {}
+    if "T" in args:
+        fields = _WEIGHTS[1:] if name == "nsos_mlp_bwd_pack_x3" else _WEIGHTS + _BIASES   # the backward packs no bias and not layer 0
+        cases.update({"null:T": {"T": None}, "packed_bytes:0": {"packed_bytes": 0},
+                      "packed_bytes:short": {"packed_bytes": getattr(lib, _PACKED_BYTES[name])(2) - 1}})
+        cases.update({f"null:T.{f}": {"T": f} for f in fields})
+    else:
+        cases["zero"] = dict({a: None for a in ptrs}, **{count: 0})
+        cases[f"{count}:-1"] = {count: -1}
+    cases.update({f"null:{a}": {a: None} for a in ptrs if a not in optional})
+    cases.update({f"misaligned:{a}": {a: "odd"} for a in ptrs if a in _ALIGNED})
+    cases["sem_mode:3"] = {"sem_mode": 3}
+    if name in _NEEDS_SEM_HEAD:
+        cases["sem_mode:0"] = {"sem_mode": 0}
+    if "dtype" in args:
+        cases.update({"dtype:0": {"dtype": 0}, "dtype:3": {"dtype": 3}})
+    if "n_rays" in args:
+        cases["n_samples:0"] = {"n_samples": 0}
+        cases["n_rays:2^31"] = {"n_rays": 1 << 31, "n_samples": 128}          # 2^31 tiles as well, for the entry points that take 2^31 rays
+        cases["tiles:2^31"] = {"n_rays": (1 << 31) - 1, "n_samples": (1 << 31) - 1}
+    if "n_pts" in args:
+        cases["n_pts:2^39"] = {"n_pts": 1 << 39}                              # 2^32 tiles of 128 points
+    for a, b in _PAIRS:
+        if a in cases and b in cases and not set(cases[a]) & set(cases[b]):
+            cases[f"{a} + {b}"] = dict(cases[a], **cases[b])
+    return cases
+
+
+def _call_mlp_entry(lib, name, change, buf):
+    """`name` with valid arguments except for `change`.  Pointers are host addresses inside `buf`: nothing may dereference them."""
+    base = C.addressof(buf)
+    assert base % 16 == 0
+    value = {"sem_mode": 2, "dtype": 1, "n_rays": 4, "n_samples": 64, "n_pts": 256, "packed_bytes": 1 << 30}
+    call = []
+    for a in _MLP_ENTRIES[name]:
+        v = change.get(a, value.get(a, base))
+        if a == "T" and v is not None:
+            t = _lib.MlpTensors()
+            for f in _WEIGHTS + _BIASES:
+                p = None if f == v else base
+                if f.startswith("pts_"):
+                    getattr(t, f[:5])[int(f[5])] = p
+                else:
+                    setattr(t, f, p)
+            v = C.byref(t)
+        elif v == "odd":
+            v = base + 8
+        call.append(v)
+    return getattr(lib, name)(*call, None)
+
+
+# Return codes of the library as it was before mlp_host.h took over the host-side checks (recorded from a build of that commit):
+# 0 ok, -1 NULL pointer, -2 bad shape, -3 unsupported, -4 buffer too small, -5 misaligned.
+_MLP_REFUSALS = {}
+for _names, _row in (
+    (("nsos_mlp_pack", "nsos_mlp_pack_fold", "nsos_mlp_pack_x3",), {
+        "null:T": -1, "packed_bytes:0": -4, "packed_bytes:short": -4, "null:T.pts_w0": -1, "null:T.pts_w1": -1, "null:T.pts_w2": -1,
+        "null:T.pts_w3": -1, "null:T.pts_w4": -1, "null:T.pts_w5": -1, "null:T.pts_w6": -1, "null:T.pts_w7": -1,
+        "null:T.alpha_w": -1, "null:T.feature_w": -1, "null:T.views_w": -1, "null:T.rgb_w": -1, "null:T.sem0_w": -1,
+        "null:T.sem2_w": -1, "null:T.pts_b0": -1, "null:T.pts_b1": -1, "null:T.pts_b2": -1, "null:T.pts_b3": -1,
+        "null:T.pts_b4": -1, "null:T.pts_b5": -1, "null:T.pts_b6": -1, "null:T.pts_b7": -1, "null:T.alpha_b": -1,
+        "null:T.feature_b": -1, "null:T.views_b": -1, "null:T.rgb_b": -1, "null:T.sem0_b": -1, "null:T.sem2_b": -1,
+        "null:packed": -1, "misaligned:packed": -5, "sem_mode:3": -3, "sem_mode:3 + misaligned:packed": -3,
+        "null:T + sem_mode:3": -1, "sem_mode:3 + packed_bytes:short": -3, "packed_bytes:short + misaligned:packed": -4,
+        "misaligned:packed + null:T.rgb_w": -5, "packed_bytes:short + null:T.pts_w3": -4,
+    }),
+    (("nsos_mlp_bwd_pack_x3",), {
+        "null:T": -1, "packed_bytes:0": -4, "packed_bytes:short": -4, "null:T.pts_w1": -1, "null:T.pts_w2": -1, "null:T.pts_w3": -1,
+        "null:T.pts_w4": -1, "null:T.pts_w5": -1, "null:T.pts_w6": -1, "null:T.pts_w7": -1, "null:T.alpha_w": -1,
+        "null:T.feature_w": -1, "null:T.views_w": -1, "null:T.rgb_w": -1, "null:T.sem0_w": -1, "null:T.sem2_w": -1,
+        "null:packed": -1, "misaligned:packed": -5, "sem_mode:3": -3, "sem_mode:3 + misaligned:packed": -3,
+        "null:T + sem_mode:3": -1, "sem_mode:3 + packed_bytes:short": -3, "packed_bytes:short + misaligned:packed": -4,
+        "misaligned:packed + null:T.rgb_w": -5, "packed_bytes:short + null:T.pts_w3": -4,
+    }),
+    (("nsos_mlp_pack_lp",), {
+        "null:T": -1, "packed_bytes:0": -4, "packed_bytes:short": -4, "null:T.pts_w0": -1, "null:T.pts_w1": -1, "null:T.pts_w2": -1,
+        "null:T.pts_w3": -1, "null:T.pts_w4": -1, "null:T.pts_w5": -1, "null:T.pts_w6": -1, "null:T.pts_w7": -1,
+        "null:T.alpha_w": -1, "null:T.feature_w": -1, "null:T.views_w": -1, "null:T.rgb_w": -1, "null:T.sem0_w": -1,
+        "null:T.sem2_w": -1, "null:T.pts_b0": -1, "null:T.pts_b1": -1, "null:T.pts_b2": -1, "null:T.pts_b3": -1,
+        "null:T.pts_b4": -1, "null:T.pts_b5": -1, "null:T.pts_b6": -1, "null:T.pts_b7": -1, "null:T.alpha_b": -1,
+        "null:T.feature_b": -1, "null:T.views_b": -1, "null:T.rgb_b": -1, "null:T.sem0_b": -1, "null:T.sem2_b": -1,
+        "null:packed": -1, "misaligned:packed": -5, "sem_mode:3": -3, "dtype:0": -3, "dtype:3": -3,
+        "sem_mode:3 + misaligned:packed": -3, "null:T + sem_mode:3": -1, "sem_mode:3 + packed_bytes:short": -3,
+        "packed_bytes:short + misaligned:packed": -4, "misaligned:packed + null:T.rgb_w": -5, "dtype:3 + packed_bytes:short": -3,
+        "dtype:0 + null:packed": -1, "packed_bytes:short + null:T.pts_w3": -4,
+    }),
+    (("nsos_mlp_pack_lp_heads",), {
+        "null:T": -1, "packed_bytes:0": -4, "packed_bytes:short": -4, "null:T.pts_w0": -1, "null:T.pts_w1": -1, "null:T.pts_w2": -1,
+        "null:T.pts_w3": -1, "null:T.pts_w4": -1, "null:T.pts_w5": -1, "null:T.pts_w6": -1, "null:T.pts_w7": -1,
+        "null:T.alpha_w": -1, "null:T.feature_w": -1, "null:T.views_w": -1, "null:T.rgb_w": -1, "null:T.sem0_w": -1,
+        "null:T.sem2_w": -1, "null:T.pts_b0": -1, "null:T.pts_b1": -1, "null:T.pts_b2": -1, "null:T.pts_b3": -1,
+        "null:T.pts_b4": -1, "null:T.pts_b5": -1, "null:T.pts_b6": -1, "null:T.pts_b7": -1, "null:T.alpha_b": -1,
+        "null:T.feature_b": -1, "null:T.views_b": -1, "null:T.rgb_b": -1, "null:T.sem0_b": -1, "null:T.sem2_b": -1,
+        "null:packed": -1, "misaligned:packed": -5, "sem_mode:3": -3, "sem_mode:0": -3, "dtype:0": -3, "dtype:3": -3,
+        "sem_mode:3 + misaligned:packed": -3, "null:T + sem_mode:3": -3, "sem_mode:3 + packed_bytes:short": -3,
+        "packed_bytes:short + misaligned:packed": -4, "misaligned:packed + null:T.rgb_w": -5, "dtype:3 + packed_bytes:short": -3,
+        "dtype:0 + null:packed": -1, "sem_mode:0 + null:T": -3, "sem_mode:0 + packed_bytes:short": -3,
+        "packed_bytes:short + null:T.pts_w3": -4,
+    }),
+    (("nsos_mlp_forward_rays", "nsos_mlp_forward_rays_fold",), {
+        "zero": 0, "n_rays:-1": -2, "null:packed": -1, "null:rays_o": -1, "null:rays_d": -1, "null:viewdirs": -1, "null:z_vals": -1,
+        "null:raw": -1, "misaligned:packed": -5, "misaligned:raw": -5, "sem_mode:3": -3, "n_samples:0": -2, "n_rays:2^31": -3,
+        "tiles:2^31": -3, "null:raw + sem_mode:3": -1, "misaligned:raw + n_rays:2^31": -5, "sem_mode:3 + misaligned:packed": -5,
+        "n_samples:0 + null:rays_o": -1, "tiles:2^31 + misaligned:raw": -5, "tiles:2^31 + sem_mode:3": -3,
+        "n_rays:2^31 + sem_mode:3": -3, "n_rays:-1 + null:packed": -1, "n_rays:-1 + misaligned:packed": -2,
+    }),
+    (("nsos_mlp_forward_rays_save", "nsos_mlp_forward_rays_save_fold",), {
+        "zero": 0, "n_rays:-1": -2, "null:packed": -1, "null:rays_o": -1, "null:rays_d": -1, "null:viewdirs": -1, "null:z_vals": -1,
+        "null:raw": -1, "null:sem_in": -1, "null:sem_hid": -1, "misaligned:packed": -5, "misaligned:raw": -5,
+        "misaligned:sem_in": -5, "misaligned:sem_hid": -5, "sem_mode:3": -3, "sem_mode:0": -3, "n_samples:0": -2, "n_rays:2^31": -3,
+        "tiles:2^31": -3, "null:raw + sem_mode:3": -3, "misaligned:raw + n_rays:2^31": -5, "sem_mode:3 + misaligned:packed": -3,
+        "n_samples:0 + null:rays_o": -1, "null:sem_in + misaligned:packed": -1, "null:sem_hid + n_samples:0": -1,
+        "sem_mode:0 + null:sem_in": -1, "sem_mode:0 + misaligned:sem_hid": -3, "sem_mode:0 + misaligned:raw": -3,
+        "sem_mode:3 + misaligned:sem_in": -3, "tiles:2^31 + misaligned:raw": -5, "tiles:2^31 + sem_mode:3": -3,
+        "n_rays:2^31 + sem_mode:3": -3, "n_rays:-1 + null:packed": -1, "n_rays:-1 + misaligned:packed": -2,
+    }),
+    (("nsos_mlp_forward_rays_save_all", "nsos_mlp_forward_rays_save_all_fold",), {
+        "zero": 0, "n_rays:-1": -2, "null:packed": -1, "null:rays_o": -1, "null:rays_d": -1, "null:viewdirs": -1, "null:z_vals": -1,
+        "null:raw": -1, "null:acts": -1, "misaligned:packed": -5, "misaligned:raw": -5, "misaligned:acts": -5, "sem_mode:3": -3,
+        "n_samples:0": -2, "n_rays:2^31": -3, "tiles:2^31": -3, "null:raw + sem_mode:3": -1, "misaligned:raw + n_rays:2^31": -5,
+        "sem_mode:3 + misaligned:packed": -5, "n_samples:0 + null:rays_o": -1, "null:acts + sem_mode:3": -1,
+        "misaligned:acts + null:raw": -5, "misaligned:acts + n_samples:0": -5, "tiles:2^31 + misaligned:raw": -5,
+        "tiles:2^31 + sem_mode:3": -3, "n_rays:2^31 + sem_mode:3": -3, "n_rays:-1 + null:packed": -1,
+        "n_rays:-1 + misaligned:packed": -2, "sem_mode:3 + misaligned:acts": -5,
+    }),
+    (("nsos_mlp_forward_rays_lp",), {
+        "zero": 0, "n_rays:-1": -2, "null:packed": -1, "null:rays_o": -1, "null:rays_d": -1, "null:viewdirs": -1, "null:z_vals": -1,
+        "null:raw": -1, "misaligned:packed": -5, "misaligned:raw": -5, "sem_mode:3": -3, "dtype:0": -3, "dtype:3": -3,
+        "n_samples:0": -2, "n_rays:2^31": -3, "tiles:2^31": -3, "null:raw + sem_mode:3": -1, "misaligned:raw + n_rays:2^31": -3,
+        "sem_mode:3 + misaligned:packed": -3, "n_samples:0 + null:rays_o": -1, "dtype:3 + n_samples:0": -2,
+        "dtype:3 + misaligned:raw": -3, "dtype:3 + n_rays:2^31": -3, "tiles:2^31 + misaligned:raw": -5,
+        "tiles:2^31 + sem_mode:3": -3, "n_rays:2^31 + sem_mode:3": -3, "n_rays:-1 + null:packed": -1,
+        "n_rays:-1 + misaligned:packed": -2, "dtype:0 + null:packed": -1,
+    }),
+    (("nsos_mlp_forward_rays_save_lp",), {
+        "zero": 0, "n_rays:-1": -2, "null:packed": -1, "null:rays_o": -1, "null:rays_d": -1, "null:viewdirs": -1, "null:z_vals": -1,
+        "null:raw": -1, "null:sem_in": -1, "null:sem_hid": -1, "misaligned:packed": -5, "misaligned:raw": -5,
+        "misaligned:sem_in": -5, "misaligned:sem_hid": -5, "sem_mode:3": -3, "sem_mode:0": -3, "dtype:0": -3, "dtype:3": -3,
+        "n_samples:0": -2, "n_rays:2^31": -3, "tiles:2^31": -3, "null:raw + sem_mode:3": -1, "misaligned:raw + n_rays:2^31": -3,
+        "sem_mode:3 + misaligned:packed": -3, "n_samples:0 + null:rays_o": -1, "dtype:3 + n_samples:0": -2,
+        "dtype:3 + misaligned:raw": -3, "dtype:3 + n_rays:2^31": -3, "null:sem_in + misaligned:packed": -1,
+        "null:sem_hid + n_samples:0": -1, "sem_mode:0 + null:sem_in": -1, "sem_mode:0 + misaligned:sem_hid": -5,
+        "sem_mode:0 + misaligned:raw": -5, "sem_mode:3 + misaligned:sem_in": -5, "tiles:2^31 + misaligned:raw": -5,
+        "tiles:2^31 + sem_mode:3": -3, "n_rays:2^31 + sem_mode:3": -3, "n_rays:-1 + null:packed": -1,
+        "n_rays:-1 + misaligned:packed": -2, "dtype:0 + null:packed": -1,
+    }),
+    (("nsos_mlp_forward_rays_save16_lp",), {
+        "zero": 0, "n_rays:-1": -2, "null:packed": -1, "null:rays_o": -1, "null:rays_d": -1, "null:viewdirs": -1, "null:z_vals": -1,
+        "null:raw": -1, "null:sem_in16": -1, "null:sem_hid16": -1, "misaligned:packed": -5, "misaligned:raw": -5,
+        "misaligned:sem_in16": -5, "misaligned:sem_hid16": -5, "sem_mode:3": -3, "sem_mode:0": -3, "dtype:0": -3, "dtype:3": -3,
+        "n_samples:0": -2, "n_rays:2^31": -3, "tiles:2^31": -3, "null:raw + sem_mode:3": -1, "misaligned:raw + n_rays:2^31": -3,
+        "sem_mode:3 + misaligned:packed": -3, "n_samples:0 + null:rays_o": -1, "dtype:3 + n_samples:0": -2,
+        "dtype:3 + misaligned:raw": -3, "dtype:3 + n_rays:2^31": -3, "sem_mode:0 + misaligned:raw": -5,
+        "null:sem_in16 + dtype:3": -1, "misaligned:sem_hid16 + null:z_vals": -5, "tiles:2^31 + misaligned:raw": -5,
+        "tiles:2^31 + sem_mode:3": -3, "n_rays:2^31 + sem_mode:3": -3, "n_rays:-1 + null:packed": -1,
+        "n_rays:-1 + misaligned:packed": -2, "dtype:0 + null:packed": -1,
+    }),
+    (("nsos_mlp_forward_rays_x3",), {
+        "zero": 0, "n_rays:-1": -2, "null:packed": -1, "null:rays_o": -1, "null:rays_d": -1, "null:viewdirs": -1, "null:z_vals": -1,
+        "null:raw": -1, "misaligned:packed": -5, "misaligned:raw": -5, "sem_mode:3": -3, "n_samples:0": -2, "n_rays:2^31": -3,
+        "tiles:2^31": -3, "null:raw + sem_mode:3": -1, "misaligned:raw + n_rays:2^31": -3, "sem_mode:3 + misaligned:packed": -3,
+        "n_samples:0 + null:rays_o": -1, "tiles:2^31 + misaligned:raw": -5, "tiles:2^31 + sem_mode:3": -3,
+        "n_rays:2^31 + sem_mode:3": -3, "n_rays:-1 + null:packed": -1, "n_rays:-1 + misaligned:packed": -2,
+    }),
+    (("nsos_mlp_forward_rays_save_x3",), {
+        "zero": 0, "n_rays:-1": -2, "null:packed": -1, "null:rays_o": -1, "null:rays_d": -1, "null:viewdirs": -1, "null:z_vals": -1,
+        "null:raw": -1, "null:sem_in": -1, "null:sem_hid": -1, "misaligned:packed": -5, "misaligned:raw": -5,
+        "misaligned:sem_in": -5, "misaligned:sem_hid": -5, "sem_mode:3": -3, "sem_mode:0": -3, "n_samples:0": -2, "n_rays:2^31": -3,
+        "tiles:2^31": -3, "null:raw + sem_mode:3": -1, "misaligned:raw + n_rays:2^31": -3, "sem_mode:3 + misaligned:packed": -3,
+        "n_samples:0 + null:rays_o": -1, "null:sem_in + misaligned:packed": -5, "null:sem_hid + n_samples:0": -2,
+        "sem_mode:0 + null:sem_in": -3, "sem_mode:0 + misaligned:sem_hid": -3, "sem_mode:0 + misaligned:raw": -5,
+        "sem_mode:3 + misaligned:sem_in": -3, "tiles:2^31 + misaligned:raw": -5, "tiles:2^31 + sem_mode:3": -3,
+        "n_rays:2^31 + sem_mode:3": -3, "n_rays:-1 + null:packed": -1, "n_rays:-1 + misaligned:packed": -2,
+    }),
+    (("nsos_mlp_forward_rays_save_all_x3", "nsos_mlp_forward_rays_save_all16_x3",), {
+        "zero": 0, "n_rays:-1": -2, "null:packed": -1, "null:rays_o": -1, "null:rays_d": -1, "null:viewdirs": -1, "null:z_vals": -1,
+        "null:raw": -1, "null:acts": -1, "null:relu_masks": -1, "misaligned:packed": -5, "misaligned:raw": -5,
+        "misaligned:acts": -5, "misaligned:relu_masks": -5, "sem_mode:3": -3, "n_samples:0": -2, "n_rays:2^31": -3,
+        "tiles:2^31": -3, "null:raw + sem_mode:3": -1, "misaligned:raw + n_rays:2^31": -3, "sem_mode:3 + misaligned:packed": -3,
+        "n_samples:0 + null:rays_o": -1, "null:acts + sem_mode:3": -3, "misaligned:acts + null:raw": -1,
+        "misaligned:acts + n_samples:0": -2, "null:relu_masks + misaligned:raw": -5, "misaligned:relu_masks + tiles:2^31": -5,
+        "tiles:2^31 + misaligned:raw": -5, "tiles:2^31 + sem_mode:3": -3, "n_rays:2^31 + sem_mode:3": -3,
+        "n_rays:-1 + null:packed": -1, "n_rays:-1 + misaligned:packed": -2, "sem_mode:3 + misaligned:acts": -3,
+    }),
+    (("nsos_mlp_profile_rays", "nsos_mlp_profile_rays_fold",), {
+        "zero": 0, "n_rays:-1": -2, "null:packed": -1, "null:rays_o": -1, "null:rays_d": -1, "null:viewdirs": -1, "null:z_vals": -1,
+        "null:raw": -1, "null:stamps": -1, "misaligned:packed": -5, "misaligned:raw": -5, "sem_mode:3": -3, "n_samples:0": -2,
+        "n_rays:2^31": -3, "tiles:2^31": -3, "null:raw + sem_mode:3": -1, "misaligned:raw + n_rays:2^31": -5,
+        "sem_mode:3 + misaligned:packed": -5, "n_samples:0 + null:rays_o": -1, "null:stamps + null:packed": -1,
+        "null:stamps + sem_mode:3": -1, "tiles:2^31 + misaligned:raw": -5, "tiles:2^31 + sem_mode:3": -3,
+        "n_rays:2^31 + sem_mode:3": -3, "n_rays:-1 + null:packed": -1, "n_rays:-1 + misaligned:packed": -2,
+    }),
+    (("nsos_mlp_profile_rays_lp",), {
+        "zero": 0, "n_rays:-1": -2, "null:packed": -1, "null:rays_o": -1, "null:rays_d": -1, "null:viewdirs": -1, "null:z_vals": -1,
+        "null:raw": -1, "null:stamps": -1, "misaligned:packed": -5, "misaligned:raw": -5, "sem_mode:3": -3, "dtype:0": -3,
+        "dtype:3": -3, "n_samples:0": -2, "n_rays:2^31": -3, "tiles:2^31": -3, "null:raw + sem_mode:3": -1,
+        "misaligned:raw + n_rays:2^31": -3, "sem_mode:3 + misaligned:packed": -3, "n_samples:0 + null:rays_o": -1,
+        "dtype:3 + n_samples:0": -2, "dtype:3 + misaligned:raw": -3, "dtype:3 + n_rays:2^31": -3, "null:stamps + null:packed": -1,
+        "null:stamps + sem_mode:3": -1, "tiles:2^31 + misaligned:raw": -5, "tiles:2^31 + sem_mode:3": -3,
+        "n_rays:2^31 + sem_mode:3": -3, "n_rays:-1 + null:packed": -1, "n_rays:-1 + misaligned:packed": -2,
+        "dtype:0 + null:packed": -1,
+    }),
+    (("nsos_mlp_profile_rays_x3",), {
+        "zero": 0, "n_rays:-1": -2, "null:packed": -1, "null:rays_o": -1, "null:rays_d": -1, "null:viewdirs": -1, "null:z_vals": -1,
+        "null:raw": -1, "null:stamps": -1, "misaligned:packed": -5, "misaligned:raw": -5, "sem_mode:3": -3, "n_samples:0": -2,
+        "n_rays:2^31": -3, "tiles:2^31": -3, "null:raw + sem_mode:3": -1, "misaligned:raw + n_rays:2^31": -3,
+        "sem_mode:3 + misaligned:packed": -3, "n_samples:0 + null:rays_o": -1, "null:stamps + null:packed": -1,
+        "null:stamps + sem_mode:3": -1, "tiles:2^31 + misaligned:raw": -5, "tiles:2^31 + sem_mode:3": -3,
+        "n_rays:2^31 + sem_mode:3": -3, "n_rays:-1 + null:packed": -1, "n_rays:-1 + misaligned:packed": -2,
+    }),
+    (("nsos_mlp_forward_points", "nsos_mlp_forward_points_fold",), {
+        "zero": 0, "n_pts:-1": -2, "null:packed": -1, "null:pts": -1, "null:dirs": -1, "null:raw": -1, "misaligned:packed": -5,
+        "misaligned:raw": -5, "sem_mode:3": -3, "n_pts:2^39": -3, "null:raw + sem_mode:3": -1, "sem_mode:3 + misaligned:packed": -5,
+        "n_pts:2^39 + misaligned:raw": -5, "n_pts:-1 + null:raw": -1, "n_pts:-1 + sem_mode:3": -2, "sem_mode:3 + n_pts:2^39": -3,
+    }),
+    (("nsos_mlp_input_grads_x3",), {
+        "zero": 0, "n_pts:-1": -2, "null:packed": -1, "null:g_raw": -1, "null:acts": -1, "null:scale": -1, "null:gbuf": -1,
+        "misaligned:packed": -5, "misaligned:acts": -5, "misaligned:relu_masks": -5, "misaligned:gbuf": -5, "sem_mode:3": -3,
+        "n_pts:2^39": -3, "sem_mode:3 + misaligned:packed": -3, "null:acts + sem_mode:3": -1, "n_pts:2^39 + misaligned:gbuf": -5,
+        "n_pts:-1 + sem_mode:3": -2, "sem_mode:3 + n_pts:2^39": -3, "sem_mode:3 + misaligned:acts": -3,
+    }),
+    (("nsos_mlp_input_grads_x3_a16",), {
+        "zero": 0, "n_pts:-1": -2, "null:packed": -1, "null:g_raw": -1, "null:acts": -1, "null:relu_masks": -1, "null:scale": -1,
+        "null:gbuf": -1, "misaligned:packed": -5, "misaligned:acts": -5, "misaligned:relu_masks": -5, "misaligned:gbuf": -5,
+        "sem_mode:3": -3, "n_pts:2^39": -3, "sem_mode:3 + misaligned:packed": -3, "null:acts + sem_mode:3": -1,
+        "n_pts:2^39 + misaligned:gbuf": -5, "n_pts:-1 + sem_mode:3": -2, "sem_mode:3 + n_pts:2^39": -3,
+        "sem_mode:3 + misaligned:acts": -3,
+    }),
+):
+    _MLP_REFUSALS.update({_n: _row for _n in _names})
+
+
+def test_mlp_entry_points_refuse_what_they_refused_before():
+    """Every shipped-architecture MLP entry point, every way of getting a call wrong, and pairs of them (which pin the ORDER of the
+    checks): the codes are literals taken from the library before the checks were shared.  All calls return before a launch."""
+    lib = _lib.lib()
+    buf = (C.c_double * 8)()
+    assert set(_MLP_REFUSALS) == set(_MLP_ENTRIES)
+    n = 0
+    for name in _MLP_ENTRIES:
+        cases = _mlp_refusal_cases(lib, name)
+        assert set(cases) == set(_MLP_REFUSALS[name]), (name, set(cases) ^ set(_MLP_REFUSALS[name]))
+        for case, change in cases.items():
+            want = _MLP_REFUSALS[name][case]
+            assert (want == 0) == (case == "zero"), (name, case)       # only the empty batch is accepted
+            assert _call_mlp_entry(lib, name, change, buf) == want, (name, case)
+            n += 1
+    assert n > 700

@@ -131,7 +131,9 @@ class DinoViT(nn.Module):
     def _ws(self, batch: int, device) -> torch.Tensor:
         """ONE workspace per device, grown to the largest batch seen (3.6 MB per image) and reused by every call, so that a
         captured call keeps valid pointers.  Calls of one module on DIFFERENT streams at the same time would race on it: give each
-        stream its own DinoViT (the packed weights are small) or order the streams."""
+        stream its own DinoViT (the packed weights are small) or order the streams.  That includes a captured training step that
+        holds this module (GraphedPatchStep(dino=...)): while one of its replays is in flight, this DinoViT must not also be called
+        from another stream -- the replay and the call would share the workspace."""
         key = str(device)
         ws = self._workspace.get(key)
         if ws is None or ws.numel() < ops.dino_workspace_floats(batch):
@@ -139,6 +141,18 @@ class DinoViT(nn.Module):
                 self._retired.append(ws)      # a graph captured at the smaller batch still points into it
             ws = self._workspace[key] = ops.dino_workspace(batch, device)
         return ws
+
+    def prepare(self, batch: int, device=None) -> None:
+        """The first call's one-time work, done now: the packed weight stream of the current `precision` and the workspace for
+        `batch` images on `device` (default: the parameters').  A stream capture calls this beforehand, so that the captured call
+        packs nothing and allocates no workspace."""
+        device = self.cls_token.device if device is None else torch.device(device)
+        if self.precision == "fp32":
+            self.packed_weights()
+            self._ws(int(batch), device)
+        else:
+            self.packed_weights16(self.precision)
+            self._ws16(int(batch), device)
 
     def _ws16(self, batch: int, device) -> torch.Tensor:
         """The 16-bit path's workspace (2.0 MB per image), one per device, by the rule of _ws; fp16 and bf16 share it."""
@@ -188,7 +202,9 @@ class DinoViT(nn.Module):
     # ---- the reference's interface
     def get_vit_attn_feat(self, x: torch.Tensor, prepared: bool = False, **want) -> Dict[str, torch.Tensor]:
         """models/extractor.py:204-213: x [B,3,h,w] -> nearest resize to 224x224, (x - mean) / std, the network;
-        {'attn' [B,1,196], 'cls_' [B,384], 'feat' [B,196,384]}.  prepared=True: x is the [B,3,224,224] network input itself."""
+        {'attn' [B,1,196], 'cls_' [B,384], 'feat' [B,196,384]}.  prepared=True: x is the [B,3,224,224] network input itself.
+        out={"feat": ..., "cls_": ...}: contiguous float32 GPU tensors of those shapes that receive the two outputs instead of fresh
+        allocations (ops.dino_forward checks them: ValueError); the returned dict holds the caller's tensors."""
         if prepared:
             if tuple(x.shape[1:]) != (3, IMAGE, IMAGE):
                 raise ValueError(f"a prepared input is [B,3,{IMAGE},{IMAGE}], got {tuple(x.shape)}")
@@ -205,7 +221,8 @@ class DinoViT(nn.Module):
         """engines/trainer.py:103-109 from the rendered patches: rgb [B,P,P,3] (or [B,3,P,P]) -> resize to P*stride, normalise,
         then get_vit_attn_feat (which resizes to 224 and normalises again).  Returns get_vit_attn_feat's dict plus 'feats'
         [B,384,14,14] (the trainer's permuted view of 'feat': CorrelationLoss' orig_feats) and 'cls_tokens' (= 'cls_': similarity_negatives /
-        NeRFContrastive)."""
+        NeRFContrastive).  out= as in get_vit_attn_feat: 'feat' / 'cls_' are then the caller's tensors, 'feats' / 'cls_tokens' the
+        view of / the same storage, and with want_attn=False the call allocates nothing (what a captured training step relies on)."""
         if patch_stride < 1:
             raise ValueError(f"patch_stride must be >= 1, got {patch_stride}")
         nhwc = rgb.dim() == 4 and rgb.shape[-1] == 3 and rgb.shape[1] != 3

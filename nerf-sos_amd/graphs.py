@@ -77,6 +77,16 @@ class GraphedPatchStep:
       * the optimizer: `capturable=True` (step count on the device);  parameters re-packed inside the graph (trainable nets
         re-pack on every call), so a replay renders with the weights the previous replay's update produced;
       * static inputs: `rays`, `feat`, `cls_tokens` are the graph's own buffers -- `load()` copies a new batch into them.
+    `dino` (a DinoViT, with the trainer's `patch_stride`; positional `feat` / `cls_tokens` must then be None): the reference's own step
+    (engines/trainer.py:101-109) -- the captured step runs the extractor on the patches it has just rendered
+    (sharding.sharded_patch_step(dino=...)) between the render and the gather, so a replay is render -> DINO -> negatives -> losses ->
+    backward -> optimizer in one launch.  The object owns static `feat` [n_local,196,384] (`feats`: its [n_local,384,14,14] view) and
+    `cls` [n_local,384]; the extractor writes them through `out=`, and after every step they hold the features of the render that
+    step made (to log or validate from).  `load(rays)` then takes the rays alone.  The extractor's packed weights and its workspace
+    for n_local patches are made before the warm-up, and the extractor is frozen (its pack key is host-side and does not change), so
+    the captured call packs nothing, allocates nothing and never synchronises; the graph holds the packed stream's and the
+    workspace's addresses, so change the extractor's weights or `precision` only together with a new capture.  DinoViT keeps ONE
+    workspace per device: do not call the same DinoViT from another stream while a replay is in flight (dino.DinoViT._ws).
     `eager_step()` runs the very same function without the graph (same generator, same counter): replay k and eager step k
     produce the same bits (tests/test_gpu_sharded.py).
 
@@ -101,9 +111,11 @@ class GraphedPatchStep:
     def __init__(self, net, optimizer, rays: torch.Tensor, bounds: Tuple[float, float], feat: torch.Tensor, cls_tokens: torch.Tensor,
                  corr_loss=None, geo_loss=None, contrast_loss=None, correlation_w: float = 1.0, geo_w: float = 0.01,
                  contrast_w: float = 0.0, seed: int = 0, overlap_losses: bool = True, warmup: int = 3, capture: bool = True,
-                 group=None, n_patches: int = None, allow_eager_fallback: bool = False, capture_collectives: bool = True):
+                 group=None, n_patches: int = None, allow_eager_fallback: bool = False, capture_collectives: bool = True, *,
+                 dino=None, patch_stride: int = None):
         import torch.distributed as dist
         from . import sharding
+        sharding.check_step_features("GraphedPatchStep", dino, patch_stride, feat, cls_tokens)
         self.group, self.capture_fallback = group, None
         multi = sharding.multi_process(group)            # collectives in the step: N > 1, or one rank under FORCE_COLLECTIVES
         if multi:
@@ -130,7 +142,17 @@ class GraphedPatchStep:
         dev = rays.device
         self.net, self.opt, self._sharding = net, optimizer, sharding
         self.n_patches = int(rays.shape[1]) if n_patches is None else int(n_patches)
-        self.rays, self.feat, self.cls = rays.clone(), feat.clone(), cls_tokens.clone()
+        self.rays = rays.clone()
+        self.dino, self.patch_stride = dino, patch_stride
+        if dino is None:
+            self.feat, self.cls = feat.clone(), cls_tokens.clone()
+        else:
+            n_local = int(rays.shape[1])
+            self.feat = torch.zeros((n_local, 196, 384), device=dev, dtype=torch.float32)
+            self.feats = self.feat.reshape(n_local, 14, 14, 384).permute(0, 3, 1, 2)      # DinoViT.patch_features' 'feats'
+            self.cls = torch.zeros((n_local, 384), device=dev, dtype=torch.float32)
+            if n_local:
+                dino.prepare(n_local, dev)               # packed weights + workspace now: the captured call makes neither
         near, far = bounds
         n_rays = self.rays[0].numel() // 3
         self.bounds = tuple(torch.full((n_rays,), float(b), device=dev, dtype=torch.float32) for b in (near, far))
@@ -190,8 +212,12 @@ class GraphedPatchStep:
 
     def _step(self):
         self.opt.zero_grad(set_to_none=True)
-        self._sharding.sharded_patch_step(self.net, self.rays, self.bounds, self.n_patches, self.feat, self.cls,
-                                          generator=self.generator, group=self.group, loss_out=self.loss, **self.losses)
+        if self.dino is None:
+            features = (self.feat, self.cls, {})
+        else:
+            features = (None, None, dict(dino=self.dino, patch_stride=self.patch_stride, dino_out={"feat": self.feat, "cls_": self.cls}))
+        self._sharding.sharded_patch_step(self.net, self.rays, self.bounds, self.n_patches, features[0], features[1],
+                                          generator=self.generator, group=self.group, loss_out=self.loss, **self.losses, **features[2])
         self.opt.step()
 
     def eager_step(self) -> torch.Tensor:
@@ -200,11 +226,22 @@ class GraphedPatchStep:
         self.steps += 1
         return self.loss
 
-    def load(self, rays: torch.Tensor, feat: torch.Tensor, cls_tokens: torch.Tensor) -> None:
-        """Copy the next batch into the graph's static input buffers (device-to-device, on the current stream)."""
+    def load(self, rays: torch.Tensor, feat: torch.Tensor = None, cls_tokens: torch.Tensor = None) -> None:
+        """Copy the next batch into the graph's static input buffers (device-to-device, on the current stream): rays, feat and
+        cls_tokens -- or, for a step built with dino=, the rays alone (the step computes the features of its own render)."""
+        self._check_load(self.dino is not None, feat, cls_tokens)
         self.rays.copy_(rays)
-        self.feat.copy_(feat)
-        self.cls.copy_(cls_tokens)
+        if self.dino is None:
+            self.feat.copy_(feat)
+            self.cls.copy_(cls_tokens)
+
+    @staticmethod
+    def _check_load(has_dino: bool, feat, cls_tokens) -> None:
+        if has_dino and (feat is not None or cls_tokens is not None):
+            raise ValueError("GraphedPatchStep.load: this step was built with dino= and computes the features of its own render -- "
+                             "load(rays) takes the rays alone")
+        if not has_dino and (feat is None or cls_tokens is None):
+            raise TypeError("GraphedPatchStep.load: load(rays, feat, cls_tokens) -- this step reads the caller's features")
 
     def __call__(self) -> torch.Tensor:
         """One training step on the loaded batch; returns the loss (a static 0-dim tensor, valid until the next call)."""

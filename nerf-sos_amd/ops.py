@@ -1268,7 +1268,29 @@ def dino_workspace16(batch: int, device) -> torch.Tensor:
     return torch.empty((dino_workspace16_floats(batch),), device=device, dtype=torch.float32)
 
 
-def _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, precision) -> Dict[str, torch.Tensor]:
+def _dino_out(out, batch: int) -> None:
+    """The host-side half of the `out=` contract of dino_forward / dino_forward16: {"feat": [B,196,384], "cls_": [B,384]}, both
+    contiguous float32 tensors.  (The device is compared with the input's once that is known to be a GPU tensor.)"""
+    if not isinstance(out, dict) or set(out) != {"feat", "cls_"}:
+        raise ValueError(f"dino: out= must be a dict with exactly the keys 'feat' and 'cls_', got "
+                         f"{sorted(out) if isinstance(out, dict) else type(out).__name__}")
+    for name, shape in (("feat", (batch, DINO_TOKENS - 1, DINO_WIDTH)), ("cls_", (batch, DINO_WIDTH))):
+        t = out[name]
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"dino: out['{name}'] must be a tensor, got {type(t).__name__}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"dino: out['{name}'] has shape {tuple(t.shape)}, the call writes {shape}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"dino: out['{name}'] must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"dino: out['{name}'] must be contiguous (strides {t.stride()}): the kernels write it densely")
+
+
+def _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, precision, out=None) -> Dict[str, torch.Tensor]:
+    if out is not None:
+        if not isinstance(x, torch.Tensor) or x.dim() != 4:
+            raise ValueError(f"dino: expected a 4-d image batch, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+        _dino_out(out, int(x.shape[0]))
     L = _lib.lib()
     f32 = precision == "fp32"
     x = _dev(x, "x")
@@ -1286,8 +1308,14 @@ def _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_pre
     if nws == 0:
         raise ValueError(f"dino: batch size {B} outside what the kernels take")
     _dino_buffer(workspace, "workspace", nws, dev)
-    out = {"feat": torch.empty((B, DINO_TOKENS - 1, DINO_WIDTH), device=dev, dtype=torch.float32),
-           "cls_": torch.empty((B, DINO_WIDTH), device=dev, dtype=torch.float32)}
+    if out is not None:
+        for name in ("feat", "cls_"):
+            if out[name].device != dev:
+                raise ValueError(f"dino: out['{name}'] is on {out[name].device}, the data on {dev}")
+        out = {"feat": out["feat"], "cls_": out["cls_"]}         # the caller's tensors; the optional outputs below are allocated
+    else:
+        out = {"feat": torch.empty((B, DINO_TOKENS - 1, DINO_WIDTH), device=dev, dtype=torch.float32),
+               "cls_": torch.empty((B, DINO_WIDTH), device=dev, dtype=torch.float32)}
     if want_attn:
         out["attn"] = torch.empty((B, 1, DINO_TOKENS - 1), device=dev, dtype=torch.float32)
     if want_prepared:
@@ -1306,19 +1334,22 @@ def _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_pre
 
 
 def dino_forward(x: torch.Tensor, packed: torch.Tensor, flags: int, patch_stride: int = 0, workspace: Optional[torch.Tensor] = None,
-                 want_attn: bool = True, want_prepared: bool = False, want_blocks: bool = False) -> Dict[str, torch.Tensor]:
+                 want_attn: bool = True, want_prepared: bool = False, want_blocks: bool = False,
+                 out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
     """`nsos_dino_forward`: x [B,h,w,3] (DINO_NHWC) or [B,3,h,w] -> {'feat' [B,196,384], 'cls_' [B,384], 'attn' [B,1,196]}
-    (+ 'prepared' [B,3,224,224], 'blocks' [12,B,197,384] on request).  Launches only; capturable."""
-    return _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, "fp32")
+    (+ 'prepared' [B,3,224,224], 'blocks' [12,B,197,384] on request).  Launches only; capturable.
+    out={"feat": ..., "cls_": ...}: contiguous float32 tensors of exactly those shapes on x's device that the kernels write instead of
+    fresh ones (ValueError otherwise); the returned dict holds them.  With want_attn=False such a call allocates nothing."""
+    return _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, "fp32", out)
 
 
 def dino_forward16(x: torch.Tensor, packed: torch.Tensor, flags: int, precision: str, patch_stride: int = 0,
                    workspace: Optional[torch.Tensor] = None, want_attn: bool = True, want_prepared: bool = False,
-                   want_blocks: bool = False) -> Dict[str, torch.Tensor]:
+                   want_blocks: bool = False, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
     """`nsos_dino_forward16`: dino_forward with the operands of every matrix product in `precision` ("fp16" / "bf16") and fp32
     accumulation; `packed` from dino_pack16 at the same precision, `workspace` from dino_workspace16.  Outputs are fp32 tensors of the
-    same keys and shapes.  Launches only; capturable."""
-    return _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, _dino_precision16(precision))
+    same keys and shapes (`out=` as in dino_forward).  Launches only; capturable."""
+    return _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, _dino_precision16(precision), out)
 
 
 def dino_resize_indices(in_size: int, patch_stride: int = 0):

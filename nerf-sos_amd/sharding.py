@@ -11,6 +11,7 @@ one flat all-gather (RCCL picks the direct algorithm at this size), never a hand
 """
 from __future__ import annotations
 
+import numbers
 import os
 from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -474,17 +475,39 @@ def _losses_and_backward(net, full, sim, s0, s1, own, gen, corr_loss, geo_loss, 
     return loss
 
 
-def sharded_patch_step(net, rays: torch.Tensor, bounds, n_patches: int, feat: torch.Tensor, cls_tokens: torch.Tensor,
+def check_step_features(who: str, dino, patch_stride, feat, cls_tokens) -> None:
+    """The one rule of `sharded_patch_step` and `graphs.GraphedPatchStep` on where a step's DINO features come from: EITHER the
+    caller's `feat` / `cls_tokens` OR an extractor (`dino`, a DinoViT, with the trainer's `patch_stride`) that the step runs on its
+    own render.  Host-side only -- no tensor's device or content is looked at."""
+    if dino is None:
+        if patch_stride is not None:
+            raise ValueError(f"{who}: patch_stride is the extractor's resize factor -- it means nothing without dino=")
+        if feat is None or cls_tokens is None:
+            raise ValueError(f"{who}: no DINO features -- pass `feat` and `cls_tokens` (features computed by the caller), or dino=<DinoViT> "
+                             "and patch_stride=<int> (features of the step's own render)")
+        return
+    from .dino import DinoViT
+    if not isinstance(dino, DinoViT):
+        raise TypeError(f"{who}: dino must be a nerf_sos_amd.DinoViT, got {type(dino).__name__}")
+    if feat is not None or cls_tokens is not None:
+        raise ValueError(f"{who}: with dino= the step computes the features from its own render -- `feat` and `cls_tokens` must be None")
+    if isinstance(patch_stride, bool) or not isinstance(patch_stride, numbers.Integral) or patch_stride < 1:
+        raise ValueError(f"{who}: dino= needs patch_stride, an integer >= 1 (the trainer's --patch_stride), got {patch_stride!r}")
+
+
+def sharded_patch_step(net, rays: torch.Tensor, bounds, n_patches: int, feat: Optional[torch.Tensor], cls_tokens: Optional[torch.Tensor],
                        corr_loss=None, geo_loss=None, correlation_w: float = 1.0, geo_w: float = 0.01, step: int = 0,
                        seed: Optional[int] = 0, group=None, timings: Optional[dict] = None,
                        overlap_losses: bool = True, contrast_loss=None, contrast_w: float = 0.0,
-                       generator: Optional[torch.Generator] = None, loss_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       generator: Optional[torch.Generator] = None, loss_out: Optional[torch.Tensor] = None, *,
+                       dino=None, patch_stride: Optional[int] = None, dino_out: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
     """One patch-mode training step of the path with the patch batch sharded over the ranks -- the loss section of
     `train_one_step` (engines/trainer.py:101-166) re-stated for one process per GPU:
 
       render this rank's patches (`rays` [2, n_local, P, P, 3], train mode)
       -> ONE flat all-gather of what the batch-wide losses read from every patch: semantics0 / semantics / fine depth,
          DINO `feat` [n_local,384,14,14] and `cls_tokens` [n_local,384] of the rank's own crops, ray_o / ray_d
+         (with `dino`: computed here, from the render above -- see below)
       -> similarity matrix of the class tokens -> negatives (utils/image.py:354)
       -> the rank's own gradient-carrying patches are spliced back into the detached batch
       -> appearance + geometric correlation losses on `semantics0` and `semantics` (engines/trainer.py:127-166); the
@@ -500,8 +523,23 @@ def sharded_patch_step(net, rays: torch.Tensor, bounds, n_patches: int, feat: to
     reference (single process only: ranks would draw different coordinates).  `generator`, if given, is used INSTEAD (a
     persistent generator the caller advances step after step -- what a captured graph of this step needs, graphs.py:
     a fresh per-step generator cannot be registered with a graph).
+
+    `dino` (a DinoViT; then `feat` and `cls_tokens` must be None and `patch_stride` is the trainer's --patch_stride): the reference's
+    own step (engines/trainer.py:101-109) -- after the rank's render the step runs
+    ``dino.patch_features(ret["rgb"].detach(), patch_stride, want_attn=False)`` on the rank's [n_local,P,P,3] patches as rendered and
+    uses its 'feats' / 'cls_tokens' where the caller's tensors went; gather, splice, negatives, both loss paths and the contrastive
+    term are unchanged.  `dino.precision` is honoured as it stands.  A rank that owns no patch does not call the extractor.  The
+    extractor is forward-only: `cls_` reaches `contrast_loss` detached, exactly like a caller-supplied `cls_tokens` -- the gradient
+    into the extractor's input (through it, into the rendered rgb) stays outside this path.  `dino_out` ({"feat": [n_local,196,384],
+    "cls_": [n_local,384]}) makes the extractor write into the caller's buffers (DinoViT.patch_features(out=...); what a captured
+    step needs to keep its features readable).
+
     `timings`, if a dict, receives HIP event pairs under 'render', 'gather', 'losses_backward' and 'allreduce' (recorded on the current stream;
-    RCCL's own stream is joined by the non-async collectives before the second event) and the gather `stats`."""
+    RCCL's own stream is joined by the non-async collectives before the second event) and the gather `stats`; with `dino` also 'dino',
+    between 'render' and 'gather' ('render' then ends where 'dino' begins)."""
+    check_step_features("sharded_patch_step", dino, patch_stride, feat, cls_tokens)
+    if dino is None and dino_out is not None:
+        raise ValueError("sharded_patch_step: dino_out names the extractor's output buffers -- it means nothing without dino=")
     rank, world = _world(group)
     own = local_patches(n_patches, rank, world)
     if rays.shape[1] != len(own):
@@ -517,6 +555,16 @@ def sharded_patch_step(net, rays: torch.Tensor, bounds, n_patches: int, feat: to
         P_ = tuple(rays.shape[2:4])
         ret = {"semantics": rays.new_zeros((0,) + P_ + (2,)), "semantics0": rays.new_zeros((0,) + P_ + (2,)),
                "depth": rays.new_zeros((0,) + P_ + (1,))}
+    ev_d = None
+    if dino is not None:
+        if ev_r is not None:
+            ev_d = torch.cuda.Event(enable_timing=True)
+            ev_d.record()
+        if len(own):
+            f = dino.patch_features(ret["rgb"].detach(), int(patch_stride), want_attn=False, **({} if dino_out is None else {"out": dino_out}))
+            feat, cls_tokens = f["feats"], f["cls_tokens"]
+        else:   # nothing rendered, nothing extracted: empty slots of the gather's widths (all_gather_patches sizes them by shape[1:])
+            feat, cls_tokens = rays.new_zeros((0, 384, 14, 14)), rays.new_zeros((0, 384))
     local = {"semantics": ret["semantics"], "semantics0": ret["semantics0"], "depth": ret["depth"],
              "feat": feat, "cls_": cls_tokens, "ray_o": rays[0], "ray_d": rays[1]}
     ev = None
@@ -548,7 +596,9 @@ def sharded_patch_step(net, rays: torch.Tensor, bounds, n_patches: int, feat: to
     all_reduce_grads(net.parameters(), group)
     if ev:
         ev[3].record()
-        timings.setdefault("render", []).append((ev_r, ev[0]))
+        timings.setdefault("render", []).append((ev_r, ev[0] if ev_d is None else ev_d))
+        if ev_d is not None:
+            timings.setdefault("dino", []).append((ev_d, ev[0]))
         timings.setdefault("gather", []).append((ev[0], ev[1]))
         timings.setdefault("losses_backward", []).append((ev[1], ev[2]))      # (with their own two reductions when N > 1)
         timings.setdefault("allreduce", []).append((ev[2], ev[3]))

@@ -2,7 +2,9 @@
 """GPU box: one training step of the shipped frozen-backbone recipe (config C3; scripts/train_fortress_node0.sh):
 render B patches of PxP rays (64+128 samples, semantic head with coordinates, train-mode perturb/noise) -> both
 correlation losses on semantics0 and semantics (engines/trainer.py:127-166) -> backward into the semantic heads ->
-Adam step.  DINO features are synthetic (the ViT is outside the path).  Prints ms/step and rays/s per precision."""
+Adam step.  DINO features are synthetic here; the step can compute them from its own render instead
+(sharding.sharded_patch_step / GraphedPatchStep with dino=<DinoViT>, patch_stride=...): scripts/bench_train_step_dino.py times
+that.  Prints ms/step and rays/s per precision."""
 import json
 import os
 import sys

@@ -13,9 +13,10 @@ Two stages, the reference's own recipe order:
      (configs/flower_full.txt);
   B. `--fix_backbone` (run_nerf.py:307-318): only semantic_linear.* trains; 8 strided 32x32 patches per step, appearance +
      geometric correlation losses on semantics0 / semantics (engines/trainer.py:127-166, scripts/train_flower_node0.sh:30-39)
-     against SYNTHETIC DINO features (the ViT is outside the path and absent): per 14x14 cell a fixed random embedding of the
+     against SYNTHETIC DINO features (no checkpoint ships with the repository): per 14x14 cell a fixed random embedding of the
      cell's foreground coverage and mean colour plus noise -- what a self-supervised ViT provides in spirit (cells of one
-     object look alike).
+     object look alike).  With a DINO checkpoint at hand the step computes real ones from its own render:
+     sharding.sharded_patch_step(..., None, None, ..., dino=<DinoViT>, patch_stride=...) / GraphedPatchStep(dino=...).
 The scene directory is written in the reference's prepared-scene layout (io.PreparedScene reads it back: the product's reader
 is what feeds the training)."""
 import argparse

@@ -394,8 +394,10 @@ extern "C" int32_t nsos_wgrad_xh(const float* G, int32_t ldg, const void* X_f16,
 // each item is its kernel + its reduction exactly as nsos_wgrad issues them (same numbers).
 extern "C" int32_t nsos_wgrad_batch(const nsos_wgrad_item* items, int32_t n_items, const float* G, int32_t ldg, const float* X, int32_t ldx,
                                     int64_t n_pts, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    NSOS_REQUIRE(n_items >= 0 && (n_items == 0 || items), NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(n_items == 0 || out, NSOS_ERR_NULL_POINTER);
+    NSOS_REQUIRE(n_items >= 0, NSOS_ERR_BAD_SHAPE);
+    NSOS_REQUIRE(n_items == 0 || (items && out), NSOS_ERR_NULL_POINTER);
+    // (an item's `G + g_col` is no longer NULL for a NULL G: wgrad_entry's own check would let it through)
+    NSOS_REQUIRE(n_items == 0 || n_pts <= 0 || (G && X), NSOS_ERR_NULL_POINTER);
     for (int i = 0; i < n_items; ++i) {
         const nsos_wgrad_item& it = items[i];
         NSOS_REQUIRE(it.g_col >= 0 && it.x_col >= 0 && it.w_off >= 0 && it.g_col + it.M <= ldg && it.x_col + it.N <= ldx, NSOS_ERR_BAD_SHAPE);

@@ -190,6 +190,65 @@ def test_split_fp16_entry_points_validate_without_a_gpu():
     assert lib.nsos_wgrad_x3(p, 256, p, 256, 64, p, 256, None, p, 1024, None) == -4                # workspace too small
 
 
+def test_wgrad_entry_points_refuse_before_any_launch():
+    """nsos_wgrad / nsos_wgrad_xh, nsos_wgrad_batch and nsos_relu_mask: every refusal below is decided on the host (fake non-null
+    pointers: nothing is dereferenced, nothing launched)."""
+    lib = _lib.lib()
+    NULL, SHAPE, UNSUPPORTED, SMALL, MISALIGNED = -1, -2, -3, -4, -5
+    buf = (C.c_double * 8)()
+    p = C.cast(buf, C.c_void_p)
+    big = 1 << 30
+    for fn in (lib.nsos_wgrad, lib.nsos_wgrad_xh):
+        #          G, ldg, X, ldx, n_pts, M, N, dW, ldw, db, workspace, workspace_bytes, stream
+        assert fn(p, 256, p, 256, 64, 256, 256, None, 256, None, p, big, None) == NULL            # dW NULL
+        assert fn(p, 256, p, 256, 64, 256, 256, p, 256, None, None, big, None) == NULL            # workspace NULL
+        assert fn(p, 256, p, 256, -1, 256, 256, p, 256, None, p, big, None) == SHAPE              # n_pts < 0
+        assert fn(None, 256, p, 256, 64, 256, 256, p, 256, None, p, big, None) == NULL            # G NULL with points to read
+        assert fn(p, 256, None, 256, 64, 256, 256, p, 256, None, p, big, None) == NULL            # X NULL with points to read
+        assert fn(p, 256, p, 256, 64, 96, 256, p, 256, None, p, big, None) == UNSUPPORTED         # M = 96
+        assert fn(p, 256, p, 256, 64, 256, 48, p, 256, None, p, big, None) == UNSUPPORTED         # N = 48
+        assert fn(p, 512, p, 256, 64, 512, 256, p, 256, None, p, big, None) == UNSUPPORTED        # M = 512
+        assert fn(p, 127, p, 64, 64, 128, 64, p, 64, None, p, big, None) == SHAPE                 # ldg < M
+        assert fn(p, 128, p, 63, 64, 128, 64, p, 64, None, p, big, None) == SHAPE                 # ldx < N
+        assert fn(p, 128, p, 64, 64, 128, 64, p, 63, None, p, big, None) == SHAPE                 # ldw < N
+        # workspace: blocks * KW * (M N + M) floats with blocks = min(256, ceil(n_pts / (2 KW))) -- one byte short
+        assert fn(p, 32, p, 256, 20, 32, 256, p, 256, None, p, 3 * 4 * (32 * 256 + 32) * 4 - 1, None) == SMALL    # KW = 4, 3 blocks
+        assert fn(p, 256, p, 256, 1 << 20, 256, 256, p, 256, None, p, 256 * (256 * 256 + 256) * 4 - 1, None) == SMALL
+        assert fn(p, 32, p, 256, 1 << 20, 32, 256, p, 256, None, p, 256 * 4 * (32 * 256 + 32) * 4 - 1, None) == SMALL
+    assert lib.nsos_wgrad_workspace_bytes() >= max(256 * (256 * 256 + 256) * 4, 256 * 4 * (32 * 256 + 32) * 4, 256 * 2 * (64 * 256 + 64) * 4)
+
+    def batch(items, n_items, G=p, ldg=300, X=p, ldx=300, n_pts=64, out=p, ws=p, ws_bytes=big):
+        arr = (_lib.WgradItem * max(len(items), 1))()
+        for i, (w, b, gc, xc, m, n, ldw) in enumerate(items):
+            arr[i].w_off, arr[i].b_off, arr[i].g_col, arr[i].x_col, arr[i].M, arr[i].N, arr[i].ldw = w, b, gc, xc, m, n, ldw
+        return lib.nsos_wgrad_batch(arr if items is not None and len(items) else None, n_items, G, ldg, X, ldx, n_pts, out, ws, ws_bytes, None)
+
+    ok = (0, -1, 0, 0, 64, 64, 64)
+    assert batch([], 0) == 0 and batch([], 0, G=None, X=None, out=None, ws=None, ws_bytes=0) == 0     # an empty list is no work
+    assert batch([ok], -1) == SHAPE                                                                   # n_items < 0
+    assert batch([], 1) == NULL                                                                       # items NULL
+    assert batch([ok], 1, out=None) == NULL
+    assert batch([ok], 1, G=None) == NULL and batch([ok], 1, X=None) == NULL                          # points to read, nothing to read from
+    assert batch([(0, -1, -1, 0, 64, 64, 64)], 1) == SHAPE                                            # g_col < 0
+    assert batch([(0, -1, 0, -1, 64, 64, 64)], 1) == SHAPE                                            # x_col < 0
+    assert batch([(-1, -1, 0, 0, 64, 64, 64)], 1) == SHAPE                                            # w_off < 0
+    assert batch([(0, -1, 300 - 63, 0, 64, 64, 64)], 1) == SHAPE                                      # g_col + M > ldg
+    assert batch([(0, -1, 0, 300 - 31, 64, 32, 64)], 1) == SHAPE                                      # x_col + N > ldx
+    assert batch([(0, -1, 0, 0, 96, 64, 64)], 1) == UNSUPPORTED                                       # the item's own refusal: M = 96
+    assert batch([(0, -1, 0, 0, 64, 64, 63)], 1) == SHAPE                                             # ... ldw < N
+    assert batch([(0, -1, 0, 0, 64, 64, 64)], 1, ws_bytes=1024) == SMALL                              # ... workspace
+    assert batch([(0, -1, 0, 0, 64, 64, 64)], 1, n_pts=-1) == SHAPE                                   # ... n_pts < 0
+
+    q = C.c_void_p(p.value + 4)                                                                        # 4-byte aligned only
+    assert p.value % 16 == 0
+    assert lib.nsos_relu_mask(None, 0, None, 0, 0, 0, None) == 0                                       # no points: nothing to do, nothing checked
+    assert lib.nsos_relu_mask(None, 64, p, 64, 8, 64, None) == NULL and lib.nsos_relu_mask(p, 64, None, 64, 8, 64, None) == NULL
+    assert lib.nsos_relu_mask(p, 64, p, 64, 8, 62, None) == SHAPE                                      # n_cols not a multiple of 4
+    assert lib.nsos_relu_mask(p, 64, p, 64, 8, 0, None) == SHAPE and lib.nsos_relu_mask(p, 64, p, 64, -8, 64, None) == SHAPE
+    assert lib.nsos_relu_mask(p, 66, p, 64, 8, 64, None) == SHAPE and lib.nsos_relu_mask(p, 64, p, 66, 8, 64, None) == SHAPE
+    assert lib.nsos_relu_mask(q, 64, p, 64, 8, 64, None) == MISALIGNED and lib.nsos_relu_mask(p, 64, q, 64, 8, 64, None) == MISALIGNED
+
+
 def test_loss_entry_points_refuse_out_of_range_shapes_and_write_nothing():
     """The correlation-loss limits -- geo N = H W <= 4096 (the LDS-resident patch), code width C in 1..4 (kMaxC), appearance
     S <= 32 (S^2 <= 1024) -- are enforced before any launch: every entry returns NSOS_ERR_UNSUPPORTED and leaves the loss and

@@ -33,7 +33,8 @@ extern "C" {
  * (GenOp::ksplit_off: an older binding's buffer sizes still agree, but the two sides must match) + nsos_wgrad_batch; 9: evaluation metrics
  * nsos_ssim, nsos_adjusted_rand, nsos_kmeans; 10: the DINO ViT-S/16 feature extractor nsos_dino_*).  The folded fp32 stream
  * (nsos_mlp_pack_fold / nsos_mlp_*_fold) only ADDS entry points -- no existing argument list or buffer format moved, so the version
- * stands; a library without them fails to bind (every declared symbol is resolved at load) and reports another source hash. */
+ * stands; a library without them fails to bind (every declared symbol is resolved at load) and reports another source hash.  The same
+ * holds for LPIPS (nsos_lpips_*): four new entry points, nothing existing moved. */
 #define NSOS_ABI_VERSION 10
 
 enum {
@@ -883,6 +884,61 @@ int32_t nsos_dino_interp_pos(const float* pos_embed, int32_t h, int32_t w, float
 size_t nsos_dino_find_fg_workspace_bytes(void);
 int32_t nsos_dino_find_fg(const int32_t* labels, const float* attn, int32_t h, int32_t w, int32_t* out_labels, float* attn_up,
                           double* means, int32_t* flipped, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- LPIPS v0.1, AlexNet (csrc/lpips.hip) ------------------------------------------------------------------------------------
+ * utils/image.py:149-160 lpips(img1, img2, net='alex') as engines/eval.py:87 calls it: lpips.LPIPS(net='alex') with lpips=True,
+ * spatial=False, in eval mode.  Forward only, fp32.  img0, img1 [N,3,H,W] (or [N,H,W,3] with NSOS_LPIPS_NHWC); with
+ * NSOS_LPIPS_NORMALIZE each is first mapped 2x - 1 (the package's normalize=True).
+ *   1. scaling layer: (x - shift[c]) / scale[c];
+ *   2. features after each ReLU: conv 3->64 k11 s4 p2 | maxpool k3 s2, conv 64->192 k5 p2 | maxpool k3 s2, conv 192->384 k3 p1 |
+ *      conv 384->256 k3 p1 | conv 256->256 k3 p1 (output extent (H + 4 - 11) / 4 + 1, pools (n - 3) / 2 + 1; H, W >= 31);
+ *   3. per layer l and pixel n(f) = f / (sqrt(sum_c f^2) + 1e-10); d_l = mean_{h,w} sum_c lin_l[c] * (n(f0) - n(f1))^2;
+ *   4. out[b] = d_0 + d_1 + d_2 + d_3 + d_4.
+ * Layout: activations are pixel-major [image][y][x][channel] with image 2b = img0[b], image 2b + 1 = img1[b].  Every convolution is
+ * one implicit GEMM (v_mfma_f32_32x32x2_f32): rows = the output pixels of all 2N images, columns = Cout, K index
+ * k = (ky * ksize + kx) * Cin + c (channel fastest: a K slice of a row is contiguous in memory), a tap outside the image contributing
+ * a = 0.  conv1's gather reads the images directly (either layout) and applies 2x - 1 and the scaling layer on the way.  The
+ * max-pools are a kernel of their own.
+ * Packed stream (nsos_lpips_packed_bytes() bytes = 4 * (8 + sum_l (Kp_l + 2) * Cout_l) with Kp = 384 (363 padded to the K tile of
+ * 32), 1600, 1728, 3456, 2304; 16-byte aligned): shift[3] + 1 zero, scale[3] + 1 zero, then per layer Wt_l [Kp_l][Cout_l] (the
+ * convolution weight transposed to the K order above, rows past K zero) and bias_l [Cout_l], then lin_0 .. lin_4.
+ * Summation orders (fixed: an image's bits do not depend on the batch, and swapping img0 and img1 changes no bit):
+ *   convolution: per output element, per K tile of 32 one fp32 fma chain over k ascending from zero; the tiles' partial sums are
+ *   added in ascending order with the rounding error of each addition carried (two-sum: tot' = fl(tot + p), lo += (tot + p) - tot'),
+ *   then fl(fl(tot + lo) + bias), then ReLU;
+ *   max-pool: dy = 0..2 outer, dx = 0..2 inner;
+ *   channel sums (sum f^2 and the lin-weighted sum; fp32): lane j of a wave adds channels j, j + 64, ... ascending, then an xor
+ *   butterfly 32, 16, 8, 4, 2, 1 over the 64 lanes;
+ *   pixels (fp64): per (layer, pair) NSOS_LPIPS_DIST_BLOCKS workgroups, workgroup g the pixels [g * chunk, (g + 1) * chunk) with
+ *   chunk = ceil(P / NSOS_LPIPS_DIST_BLOCKS), wave v of its four every 4th pixel from g * chunk + v ascending, the workgroup
+ *   ((v0 + v1) + v2) + v3; then the workgroups g ascending, / P, rounded to fp32 once; the five layers in order 0..4 in fp32.
+ * Outputs: out [batch]; optional layers [batch][5] (the d_l) and feats: the ten post-ReLU feature maps, layer after layer, layer l
+ * as [2 * batch][H_l][W_l][C_l] fp32 (pixel-major, image 2b = img0[b], 2b + 1 = img1[b]; C = 64, 192, 384, 256, 256; 16-byte aligned).
+ * Workspace: nsos_lpips_workspace_bytes(batch, h, w) bytes (0 = refused: batch outside 1..NSOS_LPIPS_MAX_BATCH, h or w outside
+ * 31..16384, or more than 2^31 GEMM rows), 16-byte aligned, contents undefined on return.
+ * Validated before anything is launched: NULL -> -1; negative batch or h, w <= 0 -> -2; batch == 0 -> 0 with no launch; h or w < 31,
+ * an unknown flag or a refused size -> -3; a misaligned pointer -> -5; a workspace too small -> -4.  No atomics, no host
+ * synchronisation, no allocation, no attribute to configure: capturable. */
+#define NSOS_LPIPS_LAYERS 5
+#define NSOS_LPIPS_MIN_SIZE 31
+#define NSOS_LPIPS_MAX_BATCH 1024
+#define NSOS_LPIPS_DIST_BLOCKS 64
+enum {
+    NSOS_LPIPS_NHWC = 1,      /* inputs [N,H,W,3] (the renderer's rgb) instead of [N,3,H,W] */
+    NSOS_LPIPS_NORMALIZE = 2  /* 2x - 1 first (inputs in [0,1] instead of [-1,1]) */
+};
+/* lpips.LPIPS's tensors (device fp32, nn.Conv2d layout as in the state dict) */
+typedef struct nsos_lpips_tensors {
+    const float *shift, *scale;            /* scaling_layer.shift / .scale            [1,3,1,1] */
+    const float* conv_w[NSOS_LPIPS_LAYERS]; /* net.slice{1..5}.{0,3,6,8,10}.weight     [64,3,11,11] [192,64,5,5] [384,192,3,3] [256,384,3,3] [256,256,3,3] */
+    const float* conv_b[NSOS_LPIPS_LAYERS]; /* ... .bias                               [Cout] */
+    const float* lin_w[NSOS_LPIPS_LAYERS];  /* lin{0..4}.model.1.weight                [1,C,1,1] */
+} nsos_lpips_tensors;
+size_t nsos_lpips_packed_bytes(void);
+int32_t nsos_lpips_pack(const nsos_lpips_tensors* tensors, void* packed, size_t packed_bytes, void* stream);
+size_t nsos_lpips_workspace_bytes(int32_t batch, int32_t h, int32_t w);
+int32_t nsos_lpips_forward(const float* img0, const float* img1, int32_t batch, int32_t h, int32_t w, int32_t flags, const void* packed,
+                           float* out, float* layers, float* feats, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

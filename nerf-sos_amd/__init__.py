@@ -15,6 +15,8 @@ from . import metrics  # noqa: F401
 from .graphs import GraphedPatchStep, GraphedRender  # noqa: F401
 from . import dino  # noqa: F401
 from .dino import DinoViT  # noqa: F401
+from . import lpips  # noqa: F401
+from .lpips import LPIPS  # noqa: F401
 from .losses import CorrelationLoss, GeoCorrelationLoss, NeRFContrastive  # noqa: F401
 
-__all__ = ["NeRFNet", "NeRFMLP", "MLP", "export_density", "ops", "sharding", "losses", "io", "synthetic", "quality", "metrics", "CorrelationLoss", "GeoCorrelationLoss", "NeRFContrastive", "GraphedRender", "GraphedPatchStep", "dino", "DinoViT"]
+__all__ = ["NeRFNet", "NeRFMLP", "MLP", "export_density", "ops", "sharding", "losses", "io", "synthetic", "quality", "metrics", "CorrelationLoss", "GeoCorrelationLoss", "NeRFContrastive", "GraphedRender", "GraphedPatchStep", "dino", "DinoViT", "lpips", "LPIPS"]

@@ -56,6 +56,14 @@ class DinoTensors(C.Structure):
     _fields_ = [("cls_token", _fp), ("pos_embed", _fp), ("patch_w", _fp), ("patch_b", _fp), ("blocks", DinoBlockTensors * DINO_DEPTH)]
 
 
+LPIPS_LAYERS = 5
+
+
+class LpipsTensors(C.Structure):
+    """struct nsos_lpips_tensors"""
+    _fields_ = [("shift", _fp), ("scale", _fp), ("conv_w", _fp * LPIPS_LAYERS), ("conv_b", _fp * LPIPS_LAYERS), ("lin_w", _fp * LPIPS_LAYERS)]
+
+
 # name -> (restype, argtypes); must list every symbol the header declares (tests/test_abi.py checks)
 SIGNATURES = {
     "nsos_abi_version": (_i32, []),
@@ -165,6 +173,10 @@ SIGNATURES = {
     "nsos_dino_interp_pos": (_i32, [C.POINTER(C.c_float), _i32, _i32, C.POINTER(C.c_float)]),
     "nsos_dino_find_fg_workspace_bytes": (_sz, []),
     "nsos_dino_find_fg": (_i32, [_fp, _fp, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
+    "nsos_lpips_packed_bytes": (_sz, []),
+    "nsos_lpips_pack": (_i32, [C.POINTER(LpipsTensors), _fp, _sz, _fp]),
+    "nsos_lpips_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "nsos_lpips_forward": (_i32, [_fp, _fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
     "nsos_corr_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "nsos_app_correlation_loss": (_i32, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                          _f32, _f32, _f32, _f32, _fp, _fp, _fp, _sz, _fp]),

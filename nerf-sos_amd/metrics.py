@@ -1,6 +1,7 @@
 """Evaluation metrics with the reference's call shapes, all on the device: SSIM (utils/image.py:139-147), sklearn's
 adjusted_rand_score, segmap_cluster (utils/misc.py:40-52) and the metric blocks of engines/eval.py:31-93 (eval_one_view) and
-engines/trainer.py:172-195 (the i_print logging) -- everything those compute except LPIPS.
+engines/trainer.py:172-195 (the i_print logging), and LPIPS (utils/image.py:149-160) through a `nerf_sos_amd.LPIPS` model that holds
+the user's weights.
 
 The clustering is sklearn's KMeans(algorithm='lloyd') with greedy k-means++ seeding, but from this package's own counter-based
 random stream (nsos_kmeans): sklearn's stream cannot be reproduced, so a seeded clustering is a different, equally valid local
@@ -28,6 +29,26 @@ def ssim(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11, size_ave
     return ops.ssim(img1.contiguous(), img2.contiguous(), window_size, size_average)
 
 
+def lpips(img1: torch.Tensor, img2: torch.Tensor, net: str = "alex", format: str = "NCHW", model=None) -> torch.Tensor:
+    """utils/image.py:149-160 with the network handed in: `model` is a nerf_sos_amd.LPIPS holding the weights (the reference builds
+    its own from the downloaded package).  format 'HWC' [H,W,3], 'NHWC' or 'NCHW'; images as the reference passes them (no 2x-1).
+    [N,1,1,1] fp32.  The HWC / NHWC layouts are read in place: no permuted copy."""
+    if net != "alex":
+        raise NotImplementedError(f"lpips: only net='alex' is built (every call site of the reference uses it), got {net!r}")
+    if model is None:
+        raise ValueError("lpips: pass model=nerf_sos_amd.LPIPS() with its weights loaded -- nothing here downloads a network")
+    if format == "HWC":
+        return model(img1[None], img2[None], nhwc=True)
+    if format == "NHWC":
+        return model(img1, img2, nhwc=True)
+    if format != "NCHW":
+        raise ValueError(f"lpips: unknown format {format!r}")
+    return model(img1, img2)
+
+
+_lpips = lpips   # view_metrics' `lpips` argument shadows the function
+
+
 def adjusted_rand_score(labels_true: torch.Tensor, labels_pred: torch.Tensor) -> torch.Tensor:
     """sklearn.metrics.adjusted_rand_score on device labelings: a 0-dim float64 tensor."""
     return ops.adjusted_rand_score(labels_true, labels_pred)[0]
@@ -51,11 +72,13 @@ def _labels_of(masks: torch.Tensor) -> torch.Tensor:
 
 
 def view_metrics(ret: Dict[str, torch.Tensor], target_s: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None,
-                 N_cluster: int = 2, clus_no_sfm: bool = False, seed: int = 0) -> Dict[str, torch.Tensor]:
-    """eval_one_view's metric_dict (mse psnr ssim clus_ari clus_ari_fg sem_ari sem_ari_fg; no lpips) plus `sem` (argmax of the
-    softmax, int32 [...,1]) and `clustering` (int32 [...,1]) on the device, from the render `ret` ('rgb' [H,W,3] and 'semantics'
-    [H,W,C]; a ray list [R,3] / [R,C] works as well, except for SSIM, which needs the image).  masks: the ground-truth labels
-    (engines/eval.py:45 `batch['masks']`), fg = masks == 1.  The ARIs and SSIM are fp32 1-element tensors, as the reference's."""
+                 N_cluster: int = 2, clus_no_sfm: bool = False, seed: int = 0, lpips=None) -> Dict[str, torch.Tensor]:
+    """eval_one_view's metric_dict (mse psnr ssim clus_ari clus_ari_fg sem_ari sem_ari_fg, and lpips when a model is given) plus
+    `sem` (argmax of the softmax, int32 [...,1]) and `clustering` (int32 [...,1]) on the device, from the render `ret` ('rgb' [H,W,3]
+    and 'semantics' [H,W,C]; a ray list [R,3] / [R,C] works as well, except for SSIM and LPIPS, which need the image).  masks: the
+    ground-truth labels (engines/eval.py:45 `batch['masks']`), fg = masks == 1.  The ARIs and SSIM are fp32 1-element tensors, as the
+    reference's.  lpips: a nerf_sos_amd.LPIPS model -> out['lpips'] [1,1,1,1] (engines/eval.py:87 lpips(rgb, target_s,
+    format='HWC')); None (the default): no 'lpips' key."""
     out: Dict[str, torch.Tensor] = {}
     sem = ret.get("semantics")
     rgb = ret.get("rgb")
@@ -65,6 +88,8 @@ def view_metrics(ret: Dict[str, torch.Tensor], target_s: Optional[torch.Tensor] 
         out["mse"], out["psnr"] = pp["mse"], pp["psnr"]
         if rgb.dim() == 3:
             out["ssim"] = ssim(rgb, target_s.to(rgb.device), format="HWC")
+            if lpips is not None:
+                out["lpips"] = _lpips(rgb, target_s.to(rgb.device), format="HWC", model=lpips)
     if sem is not None:
         dev = sem.device
         feats = sem.float() if clus_no_sfm else pp["sem_prob"]   # engines/eval.py:49-54

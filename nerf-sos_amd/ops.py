@@ -1449,3 +1449,107 @@ def dino_find_fg(labels: torch.Tensor, attn: torch.Tensor, h: int, w: int) -> Di
         _lib.check(_lib.lib().nsos_dino_find_fg(_p(labels), _p(attn), h, w, _p(out["clustering"]), _p(out["attn"]), _p(out["means"]),
                                                 _p(out["flipped"]), _p(ws), ws.numel() * 4, _stream()), "nsos_dino_find_fg")
     return out
+
+
+# ------------------------------------------------------------------------------------------ LPIPS (AlexNet)
+LPIPS_NHWC, LPIPS_NORMALIZE = 1, 2                       # flags of nsos_lpips_forward
+LPIPS_LAYERS, LPIPS_MIN_SIZE = 5, 31
+LPIPS_CHANNELS = (64, 192, 384, 256, 256)
+LPIPS_CONV_KEYS = ("net.slice1.0", "net.slice2.3", "net.slice3.6", "net.slice4.8", "net.slice5.10")
+_LPIPS_CONV_SHAPES = ((64, 3, 11, 11), (192, 64, 5, 5), (384, 192, 3, 3), (256, 384, 3, 3), (256, 256, 3, 3))
+
+
+def lpips_key_shapes():
+    """lpips.LPIPS(net='alex').state_dict() as this package keeps it: names and shapes, in the module's order."""
+    out = [("scaling_layer.shift", (1, 3, 1, 1)), ("scaling_layer.scale", (1, 3, 1, 1))]
+    for key, shp in zip(LPIPS_CONV_KEYS, _LPIPS_CONV_SHAPES):
+        out += [(key + ".weight", shp), (key + ".bias", (shp[0],))]
+    out += [(f"lin{i}.model.1.weight", (1, c, 1, 1)) for i, c in enumerate(LPIPS_CHANNELS)]
+    return out
+
+
+def lpips_feature_sizes(h: int, w: int):
+    """[(H_l, W_l)] of the five feature maps of an h x w image."""
+    a = ((h + 4 - 11) // 4 + 1, (w + 4 - 11) // 4 + 1)
+    b = ((a[0] - 3) // 2 + 1, (a[1] - 3) // 2 + 1)
+    c = ((b[0] - 3) // 2 + 1, (b[1] - 3) // 2 + 1)
+    return [a, b, c, c, c]
+
+
+def lpips_pack(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LPIPS' tensors (the names of lpips_key_shapes, on one GPU) -> the stream nsos_lpips_forward reads (`nsos_lpips_pack`)."""
+    keep = []
+    shapes = dict(lpips_key_shapes())
+
+    def ptr(name):
+        t = _dev(state[name].detach(), name)
+        if tuple(t.shape) != shapes[name]:                 # the pack kernels read exactly these extents
+            raise ValueError(f"lpips: `{name}` has shape {tuple(t.shape)}, the checkpoint's is {shapes[name]}")
+        if keep and t.device != keep[0].device:
+            raise RuntimeError(f"lpips: `{name}` is on {t.device}, the other tensors on {keep[0].device}")
+        keep.append(t)
+        return t.data_ptr()
+
+    ts = _lib.LpipsTensors()
+    ts.shift, ts.scale = ptr("scaling_layer.shift"), ptr("scaling_layer.scale")
+    for i, key in enumerate(LPIPS_CONV_KEYS):
+        ts.conv_w[i], ts.conv_b[i], ts.lin_w[i] = ptr(key + ".weight"), ptr(key + ".bias"), ptr(f"lin{i}.model.1.weight")
+    nbytes = int(_lib.lib().nsos_lpips_packed_bytes())
+    if packed is None:
+        packed = torch.empty((nbytes // 4,), device=keep[0].device, dtype=torch.float32)
+    _dino_buffer(packed, "packed", nbytes, keep[0].device)
+    with torch.cuda.device(packed.device):
+        _lib.check(_lib.lib().nsos_lpips_pack(C.byref(ts), _p(packed), packed.numel() * 4, _stream()), "nsos_lpips_pack")
+    return packed
+
+
+def lpips_workspace_floats(batch: int, h: int, w: int) -> int:
+    nbytes = int(_lib.lib().nsos_lpips_workspace_bytes(int(batch), int(h), int(w)))
+    if nbytes == 0:
+        raise ValueError(f"lpips: {batch} pairs of {h}x{w} images are outside what the kernels take (H, W in {LPIPS_MIN_SIZE}..16384, "
+                         f"1..1024 pairs)")
+    return nbytes // 4
+
+
+def lpips_workspace(batch: int, h: int, w: int, device) -> torch.Tensor:
+    return torch.empty((lpips_workspace_floats(batch, h, w),), device=device, dtype=torch.float32)
+
+
+def lpips_forward(img0: torch.Tensor, img1: torch.Tensor, packed: torch.Tensor, flags: int = 0, workspace: Optional[torch.Tensor] = None,
+                  want_layers: bool = False, want_feats: bool = False) -> Dict[str, torch.Tensor]:
+    """`nsos_lpips_forward`: img0, img1 [N,3,H,W] (or [N,H,W,3] with LPIPS_NHWC) -> {'lpips' [N,1,1,1]} (+ 'layers' [N,5], 'feats': a
+    list of five [2N,H_l,W_l,C_l] views, image 2b = img0[b], 2b+1 = img1[b], on request).  Launches only; capturable."""
+    img0, img1 = _dev(img0, "img0"), _dev(img1, "img1")
+    if img0.dim() != 4 or tuple(img0.shape) != tuple(img1.shape):
+        raise ValueError(f"lpips needs two 4-d image batches of one shape, got {tuple(img0.shape)} and {tuple(img1.shape)}")
+    if img0.device != img1.device:
+        raise RuntimeError(f"lpips: img0 is on {img0.device}, img1 on {img1.device}")
+    N = int(img0.shape[0])
+    h, w, ch = (int(img0.shape[1]), int(img0.shape[2]), int(img0.shape[3])) if flags & LPIPS_NHWC else \
+        (int(img0.shape[2]), int(img0.shape[3]), int(img0.shape[1]))
+    if ch != 3:
+        raise ValueError(f"lpips: expected 3 channels, got {tuple(img0.shape)}")
+    if h < LPIPS_MIN_SIZE or w < LPIPS_MIN_SIZE:
+        raise ValueError(f"lpips: the smallest image AlexNet's second pool accepts is {LPIPS_MIN_SIZE}x{LPIPS_MIN_SIZE}, got {h}x{w}")
+    dev = img0.device
+    out = {"lpips": torch.empty((N, 1, 1, 1), device=dev, dtype=torch.float32)}
+    if want_layers:
+        out["layers"] = torch.empty((N, LPIPS_LAYERS), device=dev, dtype=torch.float32)
+    if N == 0:
+        if want_feats:
+            out["feats"] = [torch.empty((0, a, b, c), device=dev) for (a, b), c in zip(lpips_feature_sizes(h, w), LPIPS_CHANNELS)]
+        return out
+    nws = lpips_workspace_floats(N, h, w) * 4
+    if workspace is None:
+        workspace = lpips_workspace(N, h, w, dev)
+    _dino_buffer(packed, "packed", int(_lib.lib().nsos_lpips_packed_bytes()), dev)
+    _dino_buffer(workspace, "workspace", nws, dev)
+    flat = None
+    if want_feats:
+        sizes = [2 * N * a * b * c for (a, b), c in zip(lpips_feature_sizes(h, w), LPIPS_CHANNELS)]
+        flat = torch.empty((sum(sizes),), device=dev, dtype=torch.float32)
+        out["feats"] = [t.view(2 * N, a, b, c) for t, (a, b), c in zip(flat.split(sizes), lpips_feature_sizes(h, w), LPIPS_CHANNELS)]
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nsos_lpips_forward(_p(img0), _p(img1), N, h, w, int(flags), _p(packed), _p(out["lpips"]), _p(out.get("layers")),
+                                                 _p(flat), _p(workspace), workspace.numel() * 4, _stream()), "nsos_lpips_forward")
+    return out

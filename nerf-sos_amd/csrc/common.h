@@ -48,6 +48,11 @@ static inline int32_t nsos_launch_status() {
     return e == hipSuccess ? NSOS_OK : (int32_t)e;
 }
 
+// grid of a one-element-per-thread kernel with 256-thread workgroups
+namespace nsos {
+inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
+}  // namespace nsos
+
 // torch.linspace(0, 1, n) fp32 exactly as ATen's CPU kernel evaluates it (symmetric fma form):
 // step = 1/(n-1);  i < n/2 : fma(step, i, 0)  else  fma(-step, n-1-i, 1).
 __device__ __forceinline__ float nsos_linspace01(int i, int n) {

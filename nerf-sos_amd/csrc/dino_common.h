@@ -1,5 +1,6 @@
 // What the fp32 (dino_vit.hip) and the 16-bit (dino_vit16.hip) DINO ViT-S/16 kernels share: the geometry, the resize index rule and
-// the prepared pixel (so that both paths produce the same [B,3,224,224] network input bit for bit), the wave reductions.
+// the prepared pixel (so that both paths produce the same [B,3,224,224] network input bit for bit), the wave reductions, the
+// element-wise kernels (outputs, copy, add) and the argument checks of the pack / forward entry points.
 #pragma once
 #include "common.h"
 
@@ -46,7 +47,79 @@ __device__ __forceinline__ float dino_wave_max(float v) {
     return v;
 }
 
-inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
+using nsos::blocks_for;
+
+// The element-wise kernels are templates over a tag that names the path: each .hip file instantiates its own copies (no ODR
+// question between the translation units), and a trace or a per-kernel check of the code object (tests/test_dino16_abi.py) tells
+// dino_copy_kernel<dino32_path> from dino_copy_kernel<dino16_path> as it told dino_copy_kernel from dino16_copy_kernel.
+struct dino32_path {};
+struct dino16_path {};
+
+// ---- outputs: cls = x[:,0], feat = x[:,1:], attn = mean over the heads (0..5 in order) of the saved row 0 ----------------------
+template <class Path>
+__global__ __launch_bounds__(256) void dino_outputs_kernel(const float* __restrict__ x, const float* __restrict__ row0, int batch,
+                                                           float* __restrict__ feat, float* __restrict__ cls, float* __restrict__ attn) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)batch * T * D) return;
+    const int c = (int)(e % D), t = (int)((e / D) % T), b = (int)(e / ((long long)T * D));
+    const float v = x[e];
+    if (t == 0) {
+        if (cls) cls[(size_t)b * D + c] = v;
+        if (attn && row0)
+            for (int j = c; j < NP; j += D) {
+                float s = 0.0f;
+                for (int h = 0; h < HEADS; ++h) s += row0[((size_t)b * HEADS + h) * NP + j];
+                attn[(size_t)b * NP + j] = s / (float)HEADS;
+            }
+    } else if (feat) {
+        feat[((size_t)b * NP + t - 1) * D + c] = v;
+    }
+}
+template <class Path>
+__global__ __launch_bounds__(256) void dino_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e < n) dst[e] = src[e];
+}
+template <class Path>
+__global__ __launch_bounds__(256) void dino_add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ dst, int n) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < n) dst[e] = a[e] + b[e];
+}
+
+// ---- argument checks.  The ORDER is part of the C ABI (a call that is wrong in two ways reports the first; mlp_host.h) ----------
+// every pointer of the checkpoint: NSOS_ERR_NULL_POINTER for the table itself or any of its 4 + 12 x 12 tensors
+inline int32_t dino_check_tensors(const nsos_dino_tensors* t) {
+    NSOS_REQUIRE(t && t->cls_token && t->pos_embed && t->patch_w && t->patch_b, NSOS_ERR_NULL_POINTER);
+    for (int i = 0; i < NSOS_DINO_DEPTH; ++i) {
+        const nsos_dino_block_tensors& b = t->blocks[i];
+        NSOS_REQUIRE(b.norm1_w && b.norm1_b && b.qkv_w && b.qkv_b && b.proj_w && b.proj_b && b.norm2_w && b.norm2_b && b.fc1_w &&
+                         b.fc1_b && b.fc2_w && b.fc2_b,
+                     NSOS_ERR_NULL_POINTER);
+    }
+    return NSOS_OK;
+}
+// nsos_dino_forward / nsos_dino_forward16: NULL pointer -> shape -> flag bits -> [precision] -> PREPARED -> STEP1 -> size limits ->
+// alignment -> workspace size.  `need` is the entry point's own workspace-bytes function; fp32 has no precision to refuse.
+inline int32_t dino_check_forward(const float* input, int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags,
+                                  const void* packed, const void* workspace, size_t workspace_bytes, size_t (*need)(int32_t),
+                                  bool precision_ok = true) {
+    NSOS_REQUIRE(input && packed && workspace, NSOS_ERR_NULL_POINTER);
+    NSOS_REQUIRE(batch > 0 && in_h > 0 && in_w > 0, NSOS_ERR_BAD_SHAPE);
+    NSOS_REQUIRE((flags & ~7) == 0, NSOS_ERR_UNSUPPORTED);
+    NSOS_REQUIRE(precision_ok, NSOS_ERR_UNSUPPORTED);
+    if (flags & NSOS_DINO_PREPARED) {
+        NSOS_REQUIRE(flags == NSOS_DINO_PREPARED, NSOS_ERR_UNSUPPORTED);
+        NSOS_REQUIRE(in_h == IMG && in_w == IMG, NSOS_ERR_BAD_SHAPE);
+    }
+    if (flags & NSOS_DINO_STEP1) {
+        NSOS_REQUIRE(patch_stride > 0, NSOS_ERR_BAD_SHAPE);   // an intermediate image of extent 0
+        NSOS_REQUIRE(patch_stride <= (1 << 10), NSOS_ERR_UNSUPPORTED);
+    }
+    NSOS_REQUIRE(batch <= NSOS_DINO_MAX_BATCH && in_h <= (1 << 14) && in_w <= (1 << 14), NSOS_ERR_UNSUPPORTED);
+    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)input & 3) == 0, NSOS_ERR_MISALIGNED);
+    NSOS_REQUIRE(workspace_bytes >= need(batch), NSOS_ERR_BUFFER_TOO_SMALL);
+    return NSOS_OK;
+}
 
 }  // namespace dino
 }  // namespace nsos

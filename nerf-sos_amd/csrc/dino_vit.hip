@@ -13,6 +13,7 @@
 #include "common.h"
 #include "mlp_common.h"
 #include "dino_common.h"
+#include "gemm32_tile.h"
 
 namespace {
 
@@ -53,64 +54,38 @@ __global__ __launch_bounds__(256) void dino_prepare_kernel(const float* __restri
     if (t == 0 && k < D) x[(size_t)b * T * D + k] = clspos[k];
 }
 
-// ---- GEMM: out[M,N] = epilogue(A[M,K] . Wt[K,N]).  64x64 outputs per workgroup, four waves of 32x32, K in steps of 32 through LDS.
+// ---- GEMM: out[M,N] = epilogue(A[M,K] . Wt[K,N]) on the shared 64x64x32 tile (gemm32_tile.h): dense A rows, one fma chain over K.
 enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_EMBED = 3 };
-constexpr int GM = 64, GN = 64, GK = 32, LDA = GK + 1;   // odd A stride: the 32 rows a wave reads per k fall in 32 banks
+using nsos::gemm32::GK;
+using nsos::gemm32::GM;
+using nsos::gemm32::GN;
 
 // K is a template parameter: a constant trip count, and proj (K 384) / fc2 (K 1536) show up as separate kernels in a trace.
 template <int EPI, int K>
 __global__ __launch_bounds__(256) void dino_gemm_kernel(const float* __restrict__ A, const float* __restrict__ Wt, const float* __restrict__ bias,
                                                         float* out, const float* extra, int M, int N, int np) {
-    __shared__ float As[GM * LDA];
-    __shared__ __attribute__((aligned(16))) float Bs[GK * GN];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
     const int m0 = blockIdx.y * GM, n0 = blockIdx.x * GN;
-    const int ar = tid >> 3, ak = (tid & 7) * 4;    // A tile 64x32: two float4 per thread (rows ar, ar + 32)
-    const int bk = tid >> 4, bn = (tid & 15) * 4;   // B tile 32x64: two float4 per thread (rows bk, bk + 16)
+    const int ar = nsos::gemm32::a_row(), ak = nsos::gemm32::a_k();
     const int row0 = min(m0 + ar, M - 1), row1 = min(m0 + ar + 32, M - 1);   // rows past M repeat the last one; never stored
-    float4 ra0, ra1, rb0, rb1;
-    auto gload = [&](int k0) {
-        ra0 = *reinterpret_cast<const float4*>(A + (size_t)row0 * K + k0 + ak);
-        ra1 = *reinterpret_cast<const float4*>(A + (size_t)row1 * K + k0 + ak);
-        rb0 = *reinterpret_cast<const float4*>(Wt + (size_t)(k0 + bk) * N + n0 + bn);
-        rb1 = *reinterpret_cast<const float4*>(Wt + (size_t)(k0 + bk + 16) * N + n0 + bn);
-    };
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-    gload(0);
-    const int a_off = (wm * 32 + (lane & 31)) * LDA + (lane >> 5), b_off = (lane >> 5) * GN + wn * 32 + (lane & 31);
-    for (int k0 = 0; k0 < K; k0 += GK) {
-        __syncthreads();   // the previous tile has been consumed
-        float* a0 = As + ar * LDA + ak;
-        a0[0] = ra0.x, a0[1] = ra0.y, a0[2] = ra0.z, a0[3] = ra0.w;
-        float* a1 = a0 + 32 * LDA;
-        a1[0] = ra1.x, a1[1] = ra1.y, a1[2] = ra1.z, a1[3] = ra1.w;
-        *reinterpret_cast<float4*>(Bs + bk * GN + bn) = rb0;
-        *reinterpret_cast<float4*>(Bs + (bk + 16) * GN + bn) = rb1;
-        __syncthreads();
-        if (k0 + GK < K) gload(k0 + GK);   // in flight under this tile's MFMAs
-#pragma unroll
-        for (int kk = 0; kk < GK; kk += 2)   // k ascending: one fma chain per output element
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[a_off + kk], Bs[b_off + kk * GN], acc, 0, 0, 0);
-    }
-    const int col = n0 + wn * 32 + (lane & 31);
-    const float bv = bias[col];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (row >= M) continue;
-        float v = acc[r] + bv;
-        if constexpr (EPI == EPI_GELU) v = v * 0.5f * (1.0f + erff(v * 0.70710678118654752440f));
-        if constexpr (EPI == EPI_RESIDUAL) v = extra[(size_t)row * N + col] + v;
-        if constexpr (EPI == EPI_EMBED) {   // row = b*np + t -> token row b*(np+1) + 1 + t; + pos_embed[1 + t]  (np = 196 at 224x224)
-            const int b = row / np, t = row - b * np;
-            v = v + extra[(size_t)(1 + t) * N + col];
-            out[((size_t)b * (np + 1) + 1 + t) * N + col] = v;
-        } else {
-            out[(size_t)row * N + col] = v;
-        }
-    }
+    float* out_col = out + nsos::gemm32::out_col(n0);   // column bases: one 64-bit add per row in the epilogue
+    const float* extra_col = (EPI == EPI_RESIDUAL || EPI == EPI_EMBED) ? extra + nsos::gemm32::out_col(n0) : nullptr;
+    nsos::gemm32::tile<nsos::gemm32::OneChain>(
+        K, m0, n0, M, Wt, bias, N,
+        [&](int k0, float4(&ra)[2]) {
+            ra[0] = *reinterpret_cast<const float4*>(A + (size_t)row0 * K + k0 + ak);
+            ra[1] = *reinterpret_cast<const float4*>(A + (size_t)row1 * K + k0 + ak);
+        },
+        [&](int row, int, float v) {
+            if constexpr (EPI == EPI_GELU) v = v * 0.5f * (1.0f + erff(v * 0.70710678118654752440f));
+            if constexpr (EPI == EPI_RESIDUAL) v = extra_col[(size_t)row * N] + v;
+            if constexpr (EPI == EPI_EMBED) {   // row = b*np + t -> token row b*(np+1) + 1 + t; + pos_embed[1 + t]  (np = 196 at 224x224)
+                const int b = row / np, t = row - b * np;
+                v = v + extra_col[(size_t)(1 + t) * N];
+                out_col[((size_t)b * (np + 1) + 1 + t) * N] = v;
+            } else {
+                out_col[(size_t)row * N] = v;
+            }
+        });
 }
 
 // ---- LayerNorm over 384, eps 1e-6 (biased variance about the mean, as nn.LayerNorm); one wave per row ---------------------------
@@ -230,40 +205,12 @@ __global__ __launch_bounds__(256) void dino_attention_kernel(const float* __rest
     }
 }
 
-// ---- outputs: cls = x[:,0], feat = x[:,1:], attn = mean over the heads (0..5 in order) of the saved row 0 ----------------------
-__global__ __launch_bounds__(256) void dino_outputs_kernel(const float* __restrict__ x, const float* __restrict__ row0, int batch,
-                                                           float* __restrict__ feat, float* __restrict__ cls, float* __restrict__ attn) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (long long)batch * T * D) return;
-    const int c = (int)(e % D), t = (int)((e / D) % T), b = (int)(e / ((long long)T * D));
-    const float v = x[e];
-    if (t == 0) {
-        if (cls) cls[(size_t)b * D + c] = v;
-        if (attn && row0)
-            for (int j = c; j < NP; j += D) {
-                float s = 0.0f;
-                for (int h = 0; h < HEADS; ++h) s += row0[((size_t)b * HEADS + h) * NP + j];
-                attn[(size_t)b * NP + j] = s / (float)HEADS;
-            }
-    } else if (feat) {
-        feat[((size_t)b * NP + t - 1) * D + c] = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void dino_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e < n) dst[e] = src[e];
-}
 // dst[i][o] = src[o][i]  (nn.Linear [out,in] -> the GEMM's [in,out])
 __global__ __launch_bounds__(256) void dino_transpose_kernel(const float* __restrict__ src, float* __restrict__ dst, int n_out, int n_in) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long long)n_out * n_in) return;
     const int o = (int)(e % n_out), i = (int)(e / n_out);
     dst[e] = src[(size_t)o * n_in + i];
-}
-__global__ __launch_bounds__(256) void dino_add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ dst, int n) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e < n) dst[e] = a[e] + b[e];
 }
 
 template <int EPI, int K>
@@ -601,25 +548,21 @@ extern "C" int32_t nsos_dino_resize_indices(int32_t in_size, int32_t patch_strid
 }
 
 extern "C" int32_t nsos_dino_pack(const nsos_dino_tensors* t, void* packed, size_t packed_bytes, void* stream) {
-    NSOS_REQUIRE(t && packed, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(t->cls_token && t->pos_embed && t->patch_w && t->patch_b, NSOS_ERR_NULL_POINTER);
-    for (int i = 0; i < NSOS_DINO_DEPTH; ++i) {
-        const nsos_dino_block_tensors& b = t->blocks[i];
-        NSOS_REQUIRE(b.norm1_w && b.norm1_b && b.qkv_w && b.qkv_b && b.proj_w && b.proj_b && b.norm2_w && b.norm2_b && b.fc1_w &&
-                         b.fc1_b && b.fc2_w && b.fc2_b,
-                     NSOS_ERR_NULL_POINTER);
-    }
+    NSOS_REQUIRE(packed, NSOS_ERR_NULL_POINTER);
+    if (int32_t c = dino_check_tensors(t)) return c;
     NSOS_REQUIRE(((uintptr_t)packed & 15) == 0, NSOS_ERR_MISALIGNED);
     NSOS_REQUIRE(packed_bytes >= P_SIZE * sizeof(float), NSOS_ERR_BUFFER_TOO_SMALL);
     if (int32_t c = dino_configure()) return c;
     hipStream_t st = (hipStream_t)stream;
     float* p = (float*)packed;
-    auto copy = [&](const float* src, float* dst, long long n) { dino_copy_kernel<<<blocks_for(n), 256, 0, st>>>(src, dst, n); };
+    auto copy = [&](const float* src, float* dst, long long n) {
+        dino_copy_kernel<dino32_path><<<blocks_for(n), 256, 0, st>>>(src, dst, n);
+    };
     auto transpose = [&](const float* src, float* dst, int n_out, int n_in) {
         dino_transpose_kernel<<<blocks_for((long long)n_out * n_in), 256, 0, st>>>(src, dst, n_out, n_in);
     };
     copy(t->pos_embed + D, p + P_POS + D, (long long)NP * D);
-    dino_add_kernel<<<blocks_for(D), 256, 0, st>>>(t->cls_token, t->pos_embed, p + P_POS, D);
+    dino_add_kernel<dino32_path><<<blocks_for(D), 256, 0, st>>>(t->cls_token, t->pos_embed, p + P_POS, D);
     transpose(t->patch_w, p + P_EMB_W, D, KE);
     copy(t->patch_b, p + P_EMB_B, D);
     for (int i = 0; i < NSOS_DINO_DEPTH; ++i) {
@@ -638,21 +581,8 @@ extern "C" int32_t nsos_dino_pack(const nsos_dino_tensors* t, void* packed, size
 extern "C" int32_t nsos_dino_forward(const float* input, int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags,
                                      const void* packed, void* workspace, size_t workspace_bytes, float* feat, float* cls, float* attn,
                                      float* prepared, float* blocks, void* stream) {
-    NSOS_REQUIRE(input && packed && workspace, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(batch > 0 && in_h > 0 && in_w > 0, NSOS_ERR_BAD_SHAPE);
-    NSOS_REQUIRE((flags & ~7) == 0, NSOS_ERR_UNSUPPORTED);
-    if (flags & NSOS_DINO_PREPARED) {
-        NSOS_REQUIRE(flags == NSOS_DINO_PREPARED, NSOS_ERR_UNSUPPORTED);
-        NSOS_REQUIRE(in_h == IMG && in_w == IMG, NSOS_ERR_BAD_SHAPE);
-    }
-    if (flags & NSOS_DINO_STEP1) {
-        NSOS_REQUIRE(patch_stride > 0, NSOS_ERR_BAD_SHAPE);   // an intermediate image of extent 0
-        NSOS_REQUIRE(patch_stride <= (1 << 10), NSOS_ERR_UNSUPPORTED);
-    }
-    NSOS_REQUIRE(batch <= NSOS_DINO_MAX_BATCH && in_h <= (1 << 14) && in_w <= (1 << 14), NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)input & 3) == 0, NSOS_ERR_MISALIGNED);
-    NSOS_REQUIRE(workspace_bytes >= nsos_dino_workspace_bytes(batch), NSOS_ERR_BUFFER_TOO_SMALL);
-
+    if (int32_t c = dino_check_forward(input, batch, in_h, in_w, patch_stride, flags, packed, workspace, workspace_bytes, nsos_dino_workspace_bytes))
+        return c;
     if (int32_t c = dino_configure()) return c;
     hipStream_t st = (hipStream_t)stream;
     const float* p = (const float*)packed;
@@ -675,10 +605,12 @@ extern "C" int32_t nsos_dino_forward(const float* input, int32_t batch, int32_t 
         dino_layernorm_kernel<<<(M + 3) / 4, 256, 0, st>>>(x, q + B_LN2W, q + B_LN2B, ln, M);
         launch_gemm<EPI_GELU, D>(ln, q + B_FC1W, q + B_FC1B, hid, nullptr, M, HID, st);
         launch_gemm<EPI_RESIDUAL, HID>(hid, q + B_FC2W, q + B_FC2B, x, x, M, D, st);
-        if (blocks) dino_copy_kernel<<<blocks_for((long long)M * D), 256, 0, st>>>(x, blocks + (size_t)i * M * D, (long long)M * D);
+        if (blocks)
+            dino_copy_kernel<dino32_path><<<blocks_for((long long)M * D), 256, 0, st>>>(x, blocks + (size_t)i * M * D, (long long)M * D);
     }
     if (feat || cls || attn)
-        dino_outputs_kernel<<<blocks_for((long long)M * D), 256, 0, st>>>(x, attn ? row0 : nullptr, batch, feat, cls, attn);
+        dino_outputs_kernel<dino32_path><<<blocks_for((long long)M * D), 256, 0, st>>>(x, attn ? row0 : nullptr, batch, feat, cls,
+                                                                                       attn);
     return nsos_launch_status();
 }
 
@@ -735,7 +667,7 @@ extern "C" int32_t nsos_dino_forward_full(const float* input, int32_t batch, int
     }
     if (feat || cls || attn)
         dino_full_outputs_kernel<<<blocks_for((long long)M * D), 256, 0, st>>>(x, sc0, ml0, batch, Tn, feat, cls, attn);
-    if (pos) dino_copy_kernel<<<blocks_for((long long)Tn * D), 256, 0, st>>>(table, pos, (long long)Tn * D);
+    if (pos) dino_copy_kernel<dino32_path><<<blocks_for((long long)Tn * D), 256, 0, st>>>(table, pos, (long long)Tn * D);
     return nsos_launch_status();
 }
 

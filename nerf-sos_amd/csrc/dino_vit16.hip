@@ -283,34 +283,6 @@ __global__ __launch_bounds__(256) void dino16_attention_kernel(const h16* __rest
     }
 }
 
-// ---- outputs (as dino_outputs_kernel): cls = x[:,0], feat = x[:,1:], attn = mean over the heads (0..5 in order) of the saved row 0 ----
-__global__ __launch_bounds__(256) void dino16_outputs_kernel(const float* __restrict__ x, const float* __restrict__ row0, int batch,
-                                                             float* __restrict__ feat, float* __restrict__ cls, float* __restrict__ attn) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (long long)batch * T * D) return;
-    const int c = (int)(e % D), t = (int)((e / D) % T), b = (int)(e / ((long long)T * D));
-    const float v = x[e];
-    if (t == 0) {
-        if (cls) cls[(size_t)b * D + c] = v;
-        if (attn && row0)
-            for (int j = c; j < NP; j += D) {
-                float s = 0.0f;
-                for (int h = 0; h < HEADS; ++h) s += row0[((size_t)b * HEADS + h) * NP + j];
-                attn[(size_t)b * NP + j] = s / (float)HEADS;
-            }
-    } else if (feat) {
-        feat[((size_t)b * NP + t - 1) * D + c] = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void dino16_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e < n) dst[e] = src[e];
-}
-__global__ __launch_bounds__(256) void dino16_add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ dst, int n) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e < n) dst[e] = a[e] + b[e];
-}
 // the one rounding of a weight: fp32 -> 16 bits, to nearest even, layout unchanged
 template <class P>
 __global__ __launch_bounds__(256) void dino16_round_kernel(const float* __restrict__ src, h16* __restrict__ dst, long long n) {
@@ -329,10 +301,12 @@ template <class P>
 int32_t pack16(const nsos_dino_tensors* t, void* packed, hipStream_t st) {
     float* f = (float*)packed;
     h16* hw = (h16*)((char*)packed + F_SIZE * 4);
-    auto copy = [&](const float* src, float* dst, long long n) { dino16_copy_kernel<<<blocks_for(n), 256, 0, st>>>(src, dst, n); };
+    auto copy = [&](const float* src, float* dst, long long n) {
+        dino_copy_kernel<dino16_path><<<blocks_for(n), 256, 0, st>>>(src, dst, n);
+    };
     auto round = [&](const float* src, h16* dst, long long n) { dino16_round_kernel<P><<<blocks_for(n), 256, 0, st>>>(src, dst, n); };
     copy(t->pos_embed + D, f + F_POS + D, (long long)NP * D);
-    dino16_add_kernel<<<blocks_for(D), 256, 0, st>>>(t->cls_token, t->pos_embed, f + F_POS, D);
+    dino_add_kernel<dino16_path><<<blocks_for(D), 256, 0, st>>>(t->cls_token, t->pos_embed, f + F_POS, D);
     round(t->patch_w, hw + H_EMB_W, (long long)D * KE);
     copy(t->patch_b, f + F_EMB_B, D);
     for (int i = 0; i < NSOS_DINO_DEPTH; ++i) {
@@ -375,10 +349,12 @@ int32_t forward16(const float* input, int batch, int in_h, int in_w, int patch_s
         dino16_layernorm_kernel<P><<<(M + 3) / 4, 256, 0, st>>>(x, q + FB_LN2W, q + FB_LN2B, (unsigned*)ln, M);
         launch_gemm16<P, EPI16_GELU, D, 64>(ln, g + HB_FC1W, q + FB_FC1B, hid, nullptr, M, HID, st);
         launch_gemm16<P, EPI16_RESIDUAL, HID, 32>(hid, g + HB_FC2W, q + FB_FC2B, x, x, M, D, st);
-        if (blocks) dino16_copy_kernel<<<blocks_for((long long)M * D), 256, 0, st>>>(x, blocks + (size_t)i * M * D, (long long)M * D);
+        if (blocks)
+            dino_copy_kernel<dino16_path><<<blocks_for((long long)M * D), 256, 0, st>>>(x, blocks + (size_t)i * M * D, (long long)M * D);
     }
     if (feat || cls || attn)
-        dino16_outputs_kernel<<<blocks_for((long long)M * D), 256, 0, st>>>(x, attn ? row0 : nullptr, batch, feat, cls, attn);
+        dino_outputs_kernel<dino16_path><<<blocks_for((long long)M * D), 256, 0, st>>>(x, attn ? row0 : nullptr, batch, feat, cls,
+                                                                                       attn);
     return nsos_launch_status();
 }
 
@@ -391,14 +367,8 @@ extern "C" size_t nsos_dino_workspace16_bytes(int32_t batch) {
 }
 
 extern "C" int32_t nsos_dino_pack16(const nsos_dino_tensors* t, int32_t precision, void* packed, size_t packed_bytes, void* stream) {
-    NSOS_REQUIRE(t && packed, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(t->cls_token && t->pos_embed && t->patch_w && t->patch_b, NSOS_ERR_NULL_POINTER);
-    for (int i = 0; i < NSOS_DINO_DEPTH; ++i) {
-        const nsos_dino_block_tensors& b = t->blocks[i];
-        NSOS_REQUIRE(b.norm1_w && b.norm1_b && b.qkv_w && b.qkv_b && b.proj_w && b.proj_b && b.norm2_w && b.norm2_b && b.fc1_w &&
-                         b.fc1_b && b.fc2_w && b.fc2_b,
-                     NSOS_ERR_NULL_POINTER);
-    }
+    NSOS_REQUIRE(packed, NSOS_ERR_NULL_POINTER);
+    if (int32_t c = dino_check_tensors(t)) return c;
     NSOS_REQUIRE(precision == NSOS_DTYPE_F16 || precision == NSOS_DTYPE_BF16, NSOS_ERR_UNSUPPORTED);   // fp32: nsos_dino_pack
     NSOS_REQUIRE(((uintptr_t)packed & 15) == 0, NSOS_ERR_MISALIGNED);
     NSOS_REQUIRE(packed_bytes >= P16_BYTES, NSOS_ERR_BUFFER_TOO_SMALL);
@@ -408,21 +378,9 @@ extern "C" int32_t nsos_dino_pack16(const nsos_dino_tensors* t, int32_t precisio
 extern "C" int32_t nsos_dino_forward16(const float* input, int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags,
                                        int32_t precision, const void* packed, void* workspace, size_t workspace_bytes, float* feat, float* cls,
                                        float* attn, float* prepared, float* blocks, void* stream) {
-    NSOS_REQUIRE(input && packed && workspace, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(batch > 0 && in_h > 0 && in_w > 0, NSOS_ERR_BAD_SHAPE);
-    NSOS_REQUIRE((flags & ~7) == 0, NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(precision == NSOS_DTYPE_F16 || precision == NSOS_DTYPE_BF16, NSOS_ERR_UNSUPPORTED);   // fp32: nsos_dino_forward
-    if (flags & NSOS_DINO_PREPARED) {
-        NSOS_REQUIRE(flags == NSOS_DINO_PREPARED, NSOS_ERR_UNSUPPORTED);
-        NSOS_REQUIRE(in_h == IMG && in_w == IMG, NSOS_ERR_BAD_SHAPE);
-    }
-    if (flags & NSOS_DINO_STEP1) {
-        NSOS_REQUIRE(patch_stride > 0, NSOS_ERR_BAD_SHAPE);   // an intermediate image of extent 0
-        NSOS_REQUIRE(patch_stride <= (1 << 10), NSOS_ERR_UNSUPPORTED);
-    }
-    NSOS_REQUIRE(batch <= NSOS_DINO_MAX_BATCH && in_h <= (1 << 14) && in_w <= (1 << 14), NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)input & 3) == 0, NSOS_ERR_MISALIGNED);
-    NSOS_REQUIRE(workspace_bytes >= nsos_dino_workspace16_bytes(batch), NSOS_ERR_BUFFER_TOO_SMALL);
+    if (int32_t c = dino_check_forward(input, batch, in_h, in_w, patch_stride, flags, packed, workspace, workspace_bytes,
+                                       nsos_dino_workspace16_bytes, precision == NSOS_DTYPE_F16 || precision == NSOS_DTYPE_BF16))   // fp32: nsos_dino_forward
+        return c;
     hipStream_t st = (hipStream_t)stream;
     return precision == NSOS_DTYPE_F16
                ? forward16<F16>(input, batch, in_h, in_w, patch_stride, flags, packed, workspace, feat, cls, attn, prepared, blocks, st)

@@ -10,14 +10,17 @@
 // (the header states it); no atomics; an output element of a convolution is one chain that reads its own image only, and a
 // distance workgroup reads one image pair only, so an image's bits do not depend on the batch it travels in.
 #include "common.h"
+#include "gemm32_tile.h"
 
 namespace {
 
-typedef float lpips_f32x16 __attribute__((ext_vector_type(16)));
+using nsos::blocks_for;
+using nsos::gemm32::GK;
+using nsos::gemm32::GM;
+using nsos::gemm32::GN;
 
 constexpr int NL = NSOS_LPIPS_LAYERS;
 constexpr int CIN[NL] = {3, 64, 192, 384, 256}, COUT[NL] = {64, 192, 384, 256, 256}, KS[NL] = {11, 5, 3, 3, 3};
-constexpr int GM = 64, GN = 64, GK = 32, LDA = GK + 1;   // odd A stride: the 32 rows a wave reads per k fall in 32 banks
 constexpr int kdim(int l) { return CIN[l] * KS[l] * KS[l]; }
 constexpr int kpad(int l) { return (kdim(l) + GK - 1) / GK * GK; }   // conv1: 363 -> 384, the others are multiples of 32
 constexpr int DB = NSOS_LPIPS_DIST_BLOCKS;
@@ -103,14 +106,9 @@ struct ConvArgs {
 
 template <int KSZ, int STRIDE, int PAD, bool FIRST>
 __global__ __launch_bounds__(256) void lpips_conv_kernel(ConvArgs a) {
-    __shared__ float As[GM * LDA];
-    __shared__ __attribute__((aligned(16))) float Bs[GK * GN];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
     const int nt = a.Cout / GN;
     const int m0 = (blockIdx.x / nt) * GM, n0 = (blockIdx.x % nt) * GN;
-    const int ar = tid >> 3, ak = (tid & 7) * 4;    // A tile 64x32: four consecutive k of rows ar and ar + 32 per thread
-    const int bk = tid >> 4, bn = (tid & 15) * 4;   // B tile 32x64: two float4 per thread (rows bk, bk + 16)
-    const int K = FIRST ? kpad(0) : a.Cin * KSZ * KSZ;
+    const int ar = nsos::gemm32::a_row(), ak = nsos::gemm32::a_k();
     int img[2], iy0[2], ix0[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {   // rows past M repeat the last one; never stored
@@ -125,9 +123,8 @@ __global__ __launch_bounds__(256) void lpips_conv_kernel(ConvArgs a) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) shift[c] = a.sc[c], scale[c] = a.sc[4 + c];
     }
-    float4 ra[2], rb0, rb1;
-    int ky = 0, kx = 0, c0 = 0;   // the tap and first channel of the K tile gload fetches next (not FIRST)
-    auto gload = [&](int k0) {
+    int ky = 0, kx = 0, c0 = 0;   // the tap and first channel of the K tile the loader fetches next (not FIRST)
+    auto load_a = [&](int k0, float4(&ra)[2]) {
         if constexpr (FIRST) {
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
@@ -162,44 +159,12 @@ __global__ __launch_bounds__(256) void lpips_conv_kernel(ConvArgs a) {
                 if (++kx == KSZ) kx = 0, ++ky;
             }
         }
-        rb0 = *reinterpret_cast<const float4*>(a.Wt + (size_t)(k0 + bk) * a.Cout + n0 + bn);
-        rb1 = *reinterpret_cast<const float4*>(a.Wt + (size_t)(k0 + bk + 16) * a.Cout + n0 + bn);
     };
-    lpips_f32x16 tot, lo;   // the K tiles' partial sums, added with the rounding error of every addition kept (two-sum)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) tot[i] = 0.0f, lo[i] = 0.0f;
-    gload(0);
-    const int a_off = (wm * 32 + (lane & 31)) * LDA + (lane >> 5), b_off = (lane >> 5) * GN + wn * 32 + (lane & 31);
-    for (int k0 = 0; k0 < K; k0 += GK) {
-        __syncthreads();   // the previous tile has been consumed
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            float* d = As + (ar + 32 * r) * LDA + ak;
-            d[0] = ra[r].x, d[1] = ra[r].y, d[2] = ra[r].z, d[3] = ra[r].w;
-        }
-        *reinterpret_cast<float4*>(Bs + bk * GN + bn) = rb0;
-        *reinterpret_cast<float4*>(Bs + (bk + 16) * GN + bn) = rb1;
-        __syncthreads();
-        if (k0 + GK < K) gload(k0 + GK);   // in flight under this tile's MFMAs
-        lpips_f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-#pragma unroll
-        for (int kk = 0; kk < GK; kk += 2)   // k ascending inside the tile: one fma chain of 32 products from zero
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[a_off + kk], Bs[b_off + kk * GN], acc, 0, 0, 0);
-        const lpips_f32x16 t = tot + acc, bb = t - tot;   // Knuth's two-sum: t + e = tot + acc exactly
-        lo = lo + ((tot - (t - bb)) + (acc - bb));
-        tot = t;
-    }
-    const int col = n0 + wn * 32 + (lane & 31);
-    const float bv = a.bias[col];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {   // C/D: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-        const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (row >= a.M) continue;
-        const float v = (tot[r] + lo[r]) + bv;
-        a.out[(size_t)row * a.Cout + col] = v < 0.0f ? 0.0f : v;   // ReLU; a NaN stays a NaN
-    }
+    float* out_col = a.out + nsos::gemm32::out_col(n0);   // column base: one 64-bit add per row in the epilogue
+    nsos::gemm32::tile<nsos::gemm32::TwoSumOfTiles>(FIRST ? kpad(0) : a.Cin * KSZ * KSZ, m0, n0, a.M, a.Wt, a.bias, a.Cout, load_a,
+                                                    [&](int row, int, float v) {
+                                                        out_col[(size_t)row * a.Cout] = v < 0.0f ? 0.0f : v;   // ReLU; a NaN stays a NaN
+                                                    });
 }
 
 // ---- max-pool k3 s2, no padding, floor: out[i][py][px][c] = max over dy, dx = 0..2 (dy outer) of in[i][2py + dy][2px + dx][c] ----
@@ -299,8 +264,6 @@ __global__ __launch_bounds__(64) void lpips_finish_kernel(const double* __restri
         out[b] = v;
     }
 }
-
-inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 
 template <int KSZ, int STRIDE, int PAD, bool FIRST>
 void launch_conv(const ConvArgs& a, hipStream_t st) {

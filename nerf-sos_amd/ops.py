@@ -1169,387 +1169,13 @@ def relu_mask_(g: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
     return g
 
 
-# ------------------------------------------------------------------------------------------ DINO ViT-S/16 feature extractor
-DINO_NHWC, DINO_STEP1, DINO_PREPARED = 1, 2, 4          # flags of nsos_dino_forward
-DINO_DEPTH, DINO_WIDTH, DINO_TOKENS, DINO_IMAGE = 12, 384, 197, 224
-_DINO_SHAPES = {"cls_token": (1, 1, 384), "pos_embed": (1, 197, 384), "patch_embed.proj.weight": (384, 3, 16, 16),
-                "patch_embed.proj.bias": (384,), "norm1.weight": (384,), "norm1.bias": (384,), "attn.qkv.weight": (1152, 384),
-                "attn.qkv.bias": (1152,), "attn.proj.weight": (384, 384), "attn.proj.bias": (384,), "norm2.weight": (384,),
-                "norm2.bias": (384,), "mlp.fc1.weight": (1536, 384), "mlp.fc1.bias": (1536,), "mlp.fc2.weight": (384, 1536),
-                "mlp.fc2.bias": (384,)}
-
-
-def _dino_buffer(t: torch.Tensor, name: str, nbytes: int, device) -> torch.Tensor:
-    """A kernel-side buffer: a contiguous float32 GPU tensor on `device` of at least nbytes."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-        raise RuntimeError(f"nerf_sos_amd: dino `{name}` must be a contiguous float32 GPU tensor -- this package has no CPU path")
-    if t.device != device:
-        raise RuntimeError(f"dino: `{name}` is on {t.device}, the data on {device}")
-    if t.numel() * 4 < nbytes:
-        raise ValueError(f"dino: `{name}` holds {t.numel() * 4} bytes, {nbytes} needed")
-    return t
-_DINO_BLOCK_FIELDS = (("norm1_w", "norm1.weight"), ("norm1_b", "norm1.bias"), ("qkv_w", "attn.qkv.weight"), ("qkv_b", "attn.qkv.bias"),
-                      ("proj_w", "attn.proj.weight"), ("proj_b", "attn.proj.bias"), ("norm2_w", "norm2.weight"), ("norm2_b", "norm2.bias"),
-                      ("fc1_w", "mlp.fc1.weight"), ("fc1_b", "mlp.fc1.bias"), ("fc2_w", "mlp.fc2.weight"), ("fc2_b", "mlp.fc2.bias"))
-
-
-def _dino_pack(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor], precision: str) -> torch.Tensor:
-    keep = []
-
-    def ptr(name):
-        t = _dev(state[name].detach(), name)
-        want = _DINO_SHAPES[name.split(".", 2)[2] if name.startswith("blocks.") else name]
-        if tuple(t.shape) != want:                      # the pack kernels read exactly these extents
-            raise ValueError(f"dino: `{name}` has shape {tuple(t.shape)}, the checkpoint's is {want}")
-        if keep and t.device != keep[0].device:
-            raise RuntimeError(f"dino: `{name}` is on {t.device}, the other tensors on {keep[0].device}")
-        keep.append(t)
-        return t.data_ptr()
-
-    ts = _lib.DinoTensors()
-    ts.cls_token, ts.pos_embed = ptr("cls_token"), ptr("pos_embed")
-    ts.patch_w, ts.patch_b = ptr("patch_embed.proj.weight"), ptr("patch_embed.proj.bias")
-    for i in range(DINO_DEPTH):
-        for field, name in _DINO_BLOCK_FIELDS:
-            setattr(ts.blocks[i], field, ptr(f"blocks.{i}.{name}"))
-    nbytes = int(_lib.lib().nsos_dino_packed_bytes() if precision == "fp32" else _lib.lib().nsos_dino_packed16_bytes())
-    if packed is None:
-        packed = torch.empty((nbytes // 4,), device=keep[0].device, dtype=torch.float32)
-    _dino_buffer(packed, "packed", nbytes, keep[0].device)
-    with torch.cuda.device(packed.device):
-        if precision == "fp32":
-            _lib.check(_lib.lib().nsos_dino_pack(C.byref(ts), _p(packed), packed.numel() * 4, _stream()), "nsos_dino_pack")
-        else:
-            _lib.check(_lib.lib().nsos_dino_pack16(C.byref(ts), DTYPES[precision], _p(packed), packed.numel() * 4, _stream()),
-                       "nsos_dino_pack16")
-    return packed
-
-
-def dino_pack(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """DINO's checkpoint tensors (state-dict names, on one GPU) -> the stream nsos_dino_forward reads (`nsos_dino_pack`)."""
-    return _dino_pack(state, packed, "fp32")
-
-
-DINO_PRECISIONS = ("fp32", "fp16", "bf16")
-
-
-def _dino_precision16(precision: str) -> str:
-    if precision not in ("fp16", "bf16"):
-        raise ValueError(f"dino: the 16-bit entry points take precision 'fp16' or 'bf16', got {precision!r}")
-    return precision
-
-
-def dino_pack16(state: Dict[str, torch.Tensor], precision: str, packed: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """`nsos_dino_pack16`: the stream nsos_dino_forward16 reads at `precision` ("fp16" / "bf16"): an fp32 section (pos_embed, biases,
-    LayerNorm vectors), then every matrix rounded once to 16 bits in its [out,in] layout.  Carried as a float32 tensor (raw bytes)."""
-    return _dino_pack(state, packed, _dino_precision16(precision))
-
-
-def dino_workspace_floats(batch: int) -> int:
-    nbytes = int(_lib.lib().nsos_dino_workspace_bytes(int(batch)))
-    if nbytes == 0:
-        raise ValueError(f"dino: batch size {batch} outside what the kernels take")
-    return nbytes // 4
-
-
-def dino_workspace(batch: int, device) -> torch.Tensor:
-    return torch.empty((dino_workspace_floats(batch),), device=device, dtype=torch.float32)
-
-
-def dino_workspace16_floats(batch: int) -> int:
-    """The 16-bit path's workspace (`nsos_dino_workspace16_bytes`) as a count of float32 elements (the buffer is raw bytes)."""
-    nbytes = int(_lib.lib().nsos_dino_workspace16_bytes(int(batch)))
-    if nbytes == 0:
-        raise ValueError(f"dino: batch size {batch} outside what the kernels take")
-    return nbytes // 4
-
-
-def dino_workspace16(batch: int, device) -> torch.Tensor:
-    return torch.empty((dino_workspace16_floats(batch),), device=device, dtype=torch.float32)
-
-
-def _dino_out(out, batch: int) -> None:
-    """The host-side half of the `out=` contract of dino_forward / dino_forward16: {"feat": [B,196,384], "cls_": [B,384]}, both
-    contiguous float32 tensors.  (The device is compared with the input's once that is known to be a GPU tensor.)"""
-    if not isinstance(out, dict) or set(out) != {"feat", "cls_"}:
-        raise ValueError(f"dino: out= must be a dict with exactly the keys 'feat' and 'cls_', got "
-                         f"{sorted(out) if isinstance(out, dict) else type(out).__name__}")
-    for name, shape in (("feat", (batch, DINO_TOKENS - 1, DINO_WIDTH)), ("cls_", (batch, DINO_WIDTH))):
-        t = out[name]
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"dino: out['{name}'] must be a tensor, got {type(t).__name__}")
-        if tuple(t.shape) != shape:
-            raise ValueError(f"dino: out['{name}'] has shape {tuple(t.shape)}, the call writes {shape}")
-        if t.dtype != torch.float32:
-            raise ValueError(f"dino: out['{name}'] must be float32, got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"dino: out['{name}'] must be contiguous (strides {t.stride()}): the kernels write it densely")
-
-
-def _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, precision, out=None) -> Dict[str, torch.Tensor]:
-    if out is not None:
-        if not isinstance(x, torch.Tensor) or x.dim() != 4:
-            raise ValueError(f"dino: expected a 4-d image batch, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
-        _dino_out(out, int(x.shape[0]))
-    L = _lib.lib()
-    f32 = precision == "fp32"
-    x = _dev(x, "x")
-    if x.dim() != 4:
-        raise ValueError(f"dino: expected a 4-d image batch, got {tuple(x.shape)}")
-    B = int(x.shape[0])
-    h, w, ch = (int(x.shape[1]), int(x.shape[2]), int(x.shape[3])) if flags & DINO_NHWC else (int(x.shape[2]), int(x.shape[3]), int(x.shape[1]))
-    if ch != 3:
-        raise ValueError(f"dino: expected 3 channels, got {tuple(x.shape)}")
-    dev = x.device
-    if workspace is None:
-        workspace = dino_workspace(B, dev) if f32 else dino_workspace16(B, dev)
-    _dino_buffer(packed, "packed", int(L.nsos_dino_packed_bytes() if f32 else L.nsos_dino_packed16_bytes()), dev)
-    nws = int(L.nsos_dino_workspace_bytes(B) if f32 else L.nsos_dino_workspace16_bytes(B))
-    if nws == 0:
-        raise ValueError(f"dino: batch size {B} outside what the kernels take")
-    _dino_buffer(workspace, "workspace", nws, dev)
-    if out is not None:
-        for name in ("feat", "cls_"):
-            if out[name].device != dev:
-                raise ValueError(f"dino: out['{name}'] is on {out[name].device}, the data on {dev}")
-        out = {"feat": out["feat"], "cls_": out["cls_"]}         # the caller's tensors; the optional outputs below are allocated
-    else:
-        out = {"feat": torch.empty((B, DINO_TOKENS - 1, DINO_WIDTH), device=dev, dtype=torch.float32),
-               "cls_": torch.empty((B, DINO_WIDTH), device=dev, dtype=torch.float32)}
-    if want_attn:
-        out["attn"] = torch.empty((B, 1, DINO_TOKENS - 1), device=dev, dtype=torch.float32)
-    if want_prepared:
-        out["prepared"] = torch.empty((B, 3, DINO_IMAGE, DINO_IMAGE), device=dev, dtype=torch.float32)
-    if want_blocks:
-        out["blocks"] = torch.empty((DINO_DEPTH, B, DINO_TOKENS, DINO_WIDTH), device=dev, dtype=torch.float32)
-    outs = (_p(out["feat"]), _p(out["cls_"]), _p(out.get("attn")), _p(out.get("prepared")), _p(out.get("blocks")), _stream())
-    with torch.cuda.device(dev):
-        if f32:
-            _lib.check(L.nsos_dino_forward(_p(x), B, h, w, int(patch_stride), int(flags), _p(packed), _p(workspace), workspace.numel() * 4,
-                                           *outs), "nsos_dino_forward")
-        else:
-            _lib.check(L.nsos_dino_forward16(_p(x), B, h, w, int(patch_stride), int(flags), DTYPES[precision], _p(packed), _p(workspace),
-                                             workspace.numel() * 4, *outs), "nsos_dino_forward16")
-    return out
-
-
-def dino_forward(x: torch.Tensor, packed: torch.Tensor, flags: int, patch_stride: int = 0, workspace: Optional[torch.Tensor] = None,
-                 want_attn: bool = True, want_prepared: bool = False, want_blocks: bool = False,
-                 out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
-    """`nsos_dino_forward`: x [B,h,w,3] (DINO_NHWC) or [B,3,h,w] -> {'feat' [B,196,384], 'cls_' [B,384], 'attn' [B,1,196]}
-    (+ 'prepared' [B,3,224,224], 'blocks' [12,B,197,384] on request).  Launches only; capturable.
-    out={"feat": ..., "cls_": ...}: contiguous float32 tensors of exactly those shapes on x's device that the kernels write instead of
-    fresh ones (ValueError otherwise); the returned dict holds them.  With want_attn=False such a call allocates nothing."""
-    return _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, "fp32", out)
-
-
-def dino_forward16(x: torch.Tensor, packed: torch.Tensor, flags: int, precision: str, patch_stride: int = 0,
-                   workspace: Optional[torch.Tensor] = None, want_attn: bool = True, want_prepared: bool = False,
-                   want_blocks: bool = False, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
-    """`nsos_dino_forward16`: dino_forward with the operands of every matrix product in `precision` ("fp16" / "bf16") and fp32
-    accumulation; `packed` from dino_pack16 at the same precision, `workspace` from dino_workspace16.  Outputs are fp32 tensors of the
-    same keys and shapes (`out=` as in dino_forward).  Launches only; capturable."""
-    return _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, _dino_precision16(precision), out)
-
-
-def dino_resize_indices(in_size: int, patch_stride: int = 0):
-    """The source index of each of the 224 rows / columns after the trainer's and the extractor's nearest resizes (host; the rule
-    the prepare kernel evaluates).  patch_stride 0: the extractor's resize alone."""
-    idx = (C.c_int32 * DINO_IMAGE)()
-    _lib.check(_lib.lib().nsos_dino_resize_indices(int(in_size), int(patch_stride), idx), "nsos_dino_resize_indices")
-    return list(idx)
-
-
-# ---- DINO's full-image path (get_vit_attn_feat_noresize) and find_fg (engines/eval.py:133-144)
-DINO_FULL_NHWC, DINO_FULL_NORMALIZE = 1, 2               # flags of nsos_dino_forward_full
-DINO_FULL_MAX_PATCHES, DINO_PATCH = 16384, 16
-
-
-def dino_full_workspace_floats(batch: int, h: int, w: int) -> int:
-    nbytes = int(_lib.lib().nsos_dino_full_workspace_bytes(int(batch), int(h), int(w)))
-    if nbytes == 0:
-        raise ValueError(f"dino: batch {batch} of {h}x{w} images is outside what the kernels take (H, W >= 16, "
-                         f"(H // 16) * (W // 16) <= {DINO_FULL_MAX_PATCHES}, batch <= 1024)")
-    return nbytes // 4
-
-
-def dino_full_workspace(batch: int, h: int, w: int, device) -> torch.Tensor:
-    return torch.empty((dino_full_workspace_floats(batch, h, w),), device=device, dtype=torch.float32)
-
-
-def dino_forward_full(x: torch.Tensor, packed: torch.Tensor, flags: int = 0, workspace: Optional[torch.Tensor] = None,
-                      want_attn: bool = True, want_pos: bool = False) -> Dict[str, torch.Tensor]:
-    """`nsos_dino_forward_full`: x [B,3,H,W] (or [B,H,W,3] with DINO_FULL_NHWC) at full resolution -> {'attn' [B,1,rows*cols],
-    'cls_' [B,384], 'feat' [B,rows*cols,384]} with rows, cols = H // 16, W // 16 (+ 'pos' [1 + rows*cols, 384] on request).
-    Launches only; capturable."""
-    x = _dev(x, "x")
-    if x.dim() != 4:
-        raise ValueError(f"dino: expected a 4-d image batch, got {tuple(x.shape)}")
-    B = int(x.shape[0])
-    h, w, ch = (int(x.shape[1]), int(x.shape[2]), int(x.shape[3])) if flags & DINO_FULL_NHWC else (int(x.shape[2]), int(x.shape[3]), int(x.shape[1]))
-    if ch != 3:
-        raise ValueError(f"dino: expected 3 channels, got {tuple(x.shape)}")
-    dev = x.device
-    nws = dino_full_workspace_floats(B, h, w) * 4
-    if workspace is None:
-        workspace = dino_full_workspace(B, h, w, dev)
-    _dino_buffer(packed, "packed", int(_lib.lib().nsos_dino_packed_bytes()), dev)
-    _dino_buffer(workspace, "workspace", nws, dev)
-    n = (h // DINO_PATCH) * (w // DINO_PATCH)
-    out = {"feat": torch.empty((B, n, DINO_WIDTH), device=dev, dtype=torch.float32),
-           "cls_": torch.empty((B, DINO_WIDTH), device=dev, dtype=torch.float32)}
-    if want_attn:
-        out["attn"] = torch.empty((B, 1, n), device=dev, dtype=torch.float32)
-    if want_pos:
-        out["pos"] = torch.empty((n + 1, DINO_WIDTH), device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nsos_dino_forward_full(_p(x), B, h, w, int(flags), _p(packed), _p(workspace), workspace.numel() * 4,
-                                                     _p(out["feat"]), _p(out["cls_"]), _p(out.get("attn")), _p(out.get("pos")),
-                                                     _stream()), "nsos_dino_forward_full")
-    return out
-
-
-def dino_interp_pos(pos_embed, h: int, w: int):
-    """The position table [1 + rows*cols, 384] nsos_dino_forward_full adds, from a CPU pos_embed [1,197,384] (host; the kernel's rule)."""
-    pe = pos_embed.detach().reshape(DINO_TOKENS, DINO_WIDTH).to("cpu", torch.float32).contiguous()
-    n = (int(h) // DINO_PATCH) * (int(w) // DINO_PATCH)
-    out = torch.empty((n + 1, DINO_WIDTH), dtype=torch.float32)
-    fp = C.POINTER(C.c_float)
-    _lib.check(_lib.lib().nsos_dino_interp_pos(C.cast(pe.data_ptr(), fp), int(h), int(w), C.cast(out.data_ptr(), fp)), "nsos_dino_interp_pos")
-    return out
-
-
-_FG_WS: Dict[torch.device, torch.Tensor] = {}
-
-
-def dino_find_fg(labels: torch.Tensor, attn: torch.Tensor, h: int, w: int) -> Dict[str, torch.Tensor]:
-    """`nsos_dino_find_fg` for one image: labels int32 with H*W elements (e.g. [H,W,1]), attn float32 with (H//16)*(W//16)
-    elements -> {'clustering' (labels' shape, int32, oriented), 'attn' [H,W,1] (nearest-upsampled), 'means' float64 [2]
-    (cluster 0, cluster 1), 'flipped' int32 [1]}.  Launches only: no host synchronisation."""
-    for t, name in ((labels, "clustering"), (attn, "attn")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError(f"nerf_sos_amd: `{name}` must be a GPU tensor -- this package has no CPU path")
-    if labels.dtype != torch.int32:
-        raise TypeError(f"find_fg: `clustering` must be int32, got {labels.dtype}")
-    if attn.dtype != torch.float32:
-        raise TypeError(f"find_fg: `attn` must be float32, got {attn.dtype}")
-    if labels.device != attn.device:
-        raise RuntimeError(f"find_fg: `clustering` is on {labels.device}, `attn` on {attn.device}")
-    h, w = int(h), int(w)
-    if h < DINO_PATCH or w < DINO_PATCH or labels.numel() != h * w or attn.numel() != (h // DINO_PATCH) * (w // DINO_PATCH):
-        raise ValueError(f"find_fg: clustering {tuple(labels.shape)} / attn {tuple(attn.shape)} do not fit a {h}x{w} image")
-    labels, attn = labels.contiguous(), attn.contiguous()
-    dev = labels.device
-    if dev not in _FG_WS:
-        _FG_WS[dev] = torch.empty((int(_lib.lib().nsos_dino_find_fg_workspace_bytes()) + 15) // 16 * 4, device=dev, dtype=torch.float32)
-    ws = _FG_WS[dev]
-    out = {"clustering": torch.empty_like(labels), "attn": torch.empty((h, w, 1), device=dev, dtype=torch.float32),
-           "means": torch.empty(2, device=dev, dtype=torch.float64), "flipped": torch.empty(1, device=dev, dtype=torch.int32)}
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nsos_dino_find_fg(_p(labels), _p(attn), h, w, _p(out["clustering"]), _p(out["attn"]), _p(out["means"]),
-                                                _p(out["flipped"]), _p(ws), ws.numel() * 4, _stream()), "nsos_dino_find_fg")
-    return out
-
-
-# ------------------------------------------------------------------------------------------ LPIPS (AlexNet)
-LPIPS_NHWC, LPIPS_NORMALIZE = 1, 2                       # flags of nsos_lpips_forward
-LPIPS_LAYERS, LPIPS_MIN_SIZE = 5, 31
-LPIPS_CHANNELS = (64, 192, 384, 256, 256)
-LPIPS_CONV_KEYS = ("net.slice1.0", "net.slice2.3", "net.slice3.6", "net.slice4.8", "net.slice5.10")
-_LPIPS_CONV_SHAPES = ((64, 3, 11, 11), (192, 64, 5, 5), (384, 192, 3, 3), (256, 384, 3, 3), (256, 256, 3, 3))
-
-
-def lpips_key_shapes():
-    """lpips.LPIPS(net='alex').state_dict() as this package keeps it: names and shapes, in the module's order."""
-    out = [("scaling_layer.shift", (1, 3, 1, 1)), ("scaling_layer.scale", (1, 3, 1, 1))]
-    for key, shp in zip(LPIPS_CONV_KEYS, _LPIPS_CONV_SHAPES):
-        out += [(key + ".weight", shp), (key + ".bias", (shp[0],))]
-    out += [(f"lin{i}.model.1.weight", (1, c, 1, 1)) for i, c in enumerate(LPIPS_CHANNELS)]
-    return out
-
-
-def lpips_feature_sizes(h: int, w: int):
-    """[(H_l, W_l)] of the five feature maps of an h x w image."""
-    a = ((h + 4 - 11) // 4 + 1, (w + 4 - 11) // 4 + 1)
-    b = ((a[0] - 3) // 2 + 1, (a[1] - 3) // 2 + 1)
-    c = ((b[0] - 3) // 2 + 1, (b[1] - 3) // 2 + 1)
-    return [a, b, c, c, c]
-
-
-def lpips_pack(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """LPIPS' tensors (the names of lpips_key_shapes, on one GPU) -> the stream nsos_lpips_forward reads (`nsos_lpips_pack`)."""
-    keep = []
-    shapes = dict(lpips_key_shapes())
-
-    def ptr(name):
-        t = _dev(state[name].detach(), name)
-        if tuple(t.shape) != shapes[name]:                 # the pack kernels read exactly these extents
-            raise ValueError(f"lpips: `{name}` has shape {tuple(t.shape)}, the checkpoint's is {shapes[name]}")
-        if keep and t.device != keep[0].device:
-            raise RuntimeError(f"lpips: `{name}` is on {t.device}, the other tensors on {keep[0].device}")
-        keep.append(t)
-        return t.data_ptr()
-
-    ts = _lib.LpipsTensors()
-    ts.shift, ts.scale = ptr("scaling_layer.shift"), ptr("scaling_layer.scale")
-    for i, key in enumerate(LPIPS_CONV_KEYS):
-        ts.conv_w[i], ts.conv_b[i], ts.lin_w[i] = ptr(key + ".weight"), ptr(key + ".bias"), ptr(f"lin{i}.model.1.weight")
-    nbytes = int(_lib.lib().nsos_lpips_packed_bytes())
-    if packed is None:
-        packed = torch.empty((nbytes // 4,), device=keep[0].device, dtype=torch.float32)
-    _dino_buffer(packed, "packed", nbytes, keep[0].device)
-    with torch.cuda.device(packed.device):
-        _lib.check(_lib.lib().nsos_lpips_pack(C.byref(ts), _p(packed), packed.numel() * 4, _stream()), "nsos_lpips_pack")
-    return packed
-
-
-def lpips_workspace_floats(batch: int, h: int, w: int) -> int:
-    nbytes = int(_lib.lib().nsos_lpips_workspace_bytes(int(batch), int(h), int(w)))
-    if nbytes == 0:
-        raise ValueError(f"lpips: {batch} pairs of {h}x{w} images are outside what the kernels take (H, W in {LPIPS_MIN_SIZE}..16384, "
-                         f"1..1024 pairs)")
-    return nbytes // 4
-
-
-def lpips_workspace(batch: int, h: int, w: int, device) -> torch.Tensor:
-    return torch.empty((lpips_workspace_floats(batch, h, w),), device=device, dtype=torch.float32)
-
-
-def lpips_forward(img0: torch.Tensor, img1: torch.Tensor, packed: torch.Tensor, flags: int = 0, workspace: Optional[torch.Tensor] = None,
-                  want_layers: bool = False, want_feats: bool = False) -> Dict[str, torch.Tensor]:
-    """`nsos_lpips_forward`: img0, img1 [N,3,H,W] (or [N,H,W,3] with LPIPS_NHWC) -> {'lpips' [N,1,1,1]} (+ 'layers' [N,5], 'feats': a
-    list of five [2N,H_l,W_l,C_l] views, image 2b = img0[b], 2b+1 = img1[b], on request).  Launches only; capturable."""
-    img0, img1 = _dev(img0, "img0"), _dev(img1, "img1")
-    if img0.dim() != 4 or tuple(img0.shape) != tuple(img1.shape):
-        raise ValueError(f"lpips needs two 4-d image batches of one shape, got {tuple(img0.shape)} and {tuple(img1.shape)}")
-    if img0.device != img1.device:
-        raise RuntimeError(f"lpips: img0 is on {img0.device}, img1 on {img1.device}")
-    N = int(img0.shape[0])
-    h, w, ch = (int(img0.shape[1]), int(img0.shape[2]), int(img0.shape[3])) if flags & LPIPS_NHWC else \
-        (int(img0.shape[2]), int(img0.shape[3]), int(img0.shape[1]))
-    if ch != 3:
-        raise ValueError(f"lpips: expected 3 channels, got {tuple(img0.shape)}")
-    if h < LPIPS_MIN_SIZE or w < LPIPS_MIN_SIZE:
-        raise ValueError(f"lpips: the smallest image AlexNet's second pool accepts is {LPIPS_MIN_SIZE}x{LPIPS_MIN_SIZE}, got {h}x{w}")
-    dev = img0.device
-    out = {"lpips": torch.empty((N, 1, 1, 1), device=dev, dtype=torch.float32)}
-    if want_layers:
-        out["layers"] = torch.empty((N, LPIPS_LAYERS), device=dev, dtype=torch.float32)
-    if N == 0:
-        if want_feats:
-            out["feats"] = [torch.empty((0, a, b, c), device=dev) for (a, b), c in zip(lpips_feature_sizes(h, w), LPIPS_CHANNELS)]
-        return out
-    nws = lpips_workspace_floats(N, h, w) * 4
-    if workspace is None:
-        workspace = lpips_workspace(N, h, w, dev)
-    _dino_buffer(packed, "packed", int(_lib.lib().nsos_lpips_packed_bytes()), dev)
-    _dino_buffer(workspace, "workspace", nws, dev)
-    flat = None
-    if want_feats:
-        sizes = [2 * N * a * b * c for (a, b), c in zip(lpips_feature_sizes(h, w), LPIPS_CHANNELS)]
-        flat = torch.empty((sum(sizes),), device=dev, dtype=torch.float32)
-        out["feats"] = [t.view(2 * N, a, b, c) for t, (a, b), c in zip(flat.split(sizes), lpips_feature_sizes(h, w), LPIPS_CHANNELS)]
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nsos_lpips_forward(_p(img0), _p(img1), N, h, w, int(flags), _p(packed), _p(out["lpips"]), _p(out.get("layers")),
-                                                 _p(flat), _p(workspace), workspace.numel() * 4, _stream()), "nsos_lpips_forward")
-    return out
+# ------------------------------------------------------------------------------------------ the image models (DINO ViT-S/16, LPIPS)
+# live in image_ops.py, which imports the helpers above (hence the import down here); every name they had in this module stays.
+from .image_ops import (  # noqa: E402,F401
+    DINO_NHWC, DINO_STEP1, DINO_PREPARED, DINO_DEPTH, DINO_WIDTH, DINO_TOKENS, DINO_IMAGE, DINO_PRECISIONS,
+    DINO_FULL_NHWC, DINO_FULL_NORMALIZE, DINO_FULL_MAX_PATCHES, DINO_PATCH,
+    dino_pack, dino_pack16, dino_workspace_floats, dino_workspace, dino_workspace16_floats, dino_workspace16,
+    dino_forward, dino_forward16, _dino_forward, dino_resize_indices,
+    dino_full_workspace_floats, dino_full_workspace, dino_forward_full, dino_interp_pos, dino_find_fg,
+    LPIPS_NHWC, LPIPS_NORMALIZE, LPIPS_LAYERS, LPIPS_MIN_SIZE, LPIPS_CHANNELS, LPIPS_CONV_KEYS, _LPIPS_CONV_SHAPES,
+    lpips_key_shapes, lpips_feature_sizes, lpips_pack, lpips_workspace_floats, lpips_workspace, lpips_forward)

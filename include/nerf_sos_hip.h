@@ -34,7 +34,7 @@ extern "C" {
  * nsos_ssim, nsos_adjusted_rand, nsos_kmeans; 10: the DINO ViT-S/16 feature extractor nsos_dino_*).  The folded fp32 stream
  * (nsos_mlp_pack_fold / nsos_mlp_*_fold) only ADDS entry points -- no existing argument list or buffer format moved, so the version
  * stands; a library without them fails to bind (every declared symbol is resolved at load) and reports another source hash.  The same
- * holds for LPIPS (nsos_lpips_*): four new entry points, nothing existing moved. */
+ * holds for LPIPS (nsos_lpips_*): four new entry points, nothing existing moved -- and for the camera layer (nsos_camera_*): three. */
 #define NSOS_ABI_VERSION 10
 
 enum {
@@ -939,6 +939,50 @@ int32_t nsos_lpips_pack(const nsos_lpips_tensors* tensors, void* packed, size_t 
 size_t nsos_lpips_workspace_bytes(int32_t batch, int32_t h, int32_t w);
 int32_t nsos_lpips_forward(const float* img0, const float* img1, int32_t batch, int32_t h, int32_t w, int32_t flags, const void* packed,
                            float* out, float* layers, float* feats, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- CameraTransformer: learnable per-camera pose corrections (csrc/camera.hip) ----------------------------------------------
+ * models/camera.py:81-143.  Per camera c a quaternion rvec[c] = (x, y, z, w) -- w LAST -- and an offset tvec[c]; ray n carries
+ * the camera id c = cam_ids[n] (int32).  All tensors fp32, dense: rays_o, rays_d, out_o, out_d [n_rays,3]; rvec [n_cams,4];
+ * tvec [n_cams,3].
+ * Forward (camera.py:103-143), every operation rounded to fp32 on its own (no contraction), in the reference's order:
+ *   theta = sqrt(1e-5 + ((x x + y y) + z z) + w w);  (a, b, c, w') = rvec[c] / theta    -- the epsilon sits INSIDE the root, so
+ *   the normalised quaternion is not exactly unit and R below is not exactly orthogonal: the backward differentiates THIS map;
+ *   R = [ (1 - 2 b b) - 2 c c    2 (a b - c w')        2 (a c + b w')
+ *         2 (a b + c w')         (1 - 2 a a) - 2 c c   2 (b c - a w')
+ *         2 (a c - b w')         2 (a w' + b c)        (1 - 2 a a) - 2 b b ];
+ *   out_d[n][i] = (d[0] R[i][0] + d[1] R[i][1]) + d[2] R[i][2];   out_o[n] = o[n] + tvec[c]  (one rounded add).
+ *   The identity (0,0,0,1) returns its input bit for bit (every product is by an exact 0 or 1).
+ * Backward.  g_tvec[c] = sum_{n: id = c} g_out_o[n];  G[c] = sum_{n: id = c} g_out_d[n] (x) d[n]  (3x3);  g_qhat = the contraction of
+ * G with dR / d(a, b, c, w') (R is quadratic: a 4-vector);  g_rvec[c] = g_qhat / theta - rvec[c] (rvec[c] . g_qhat) / theta^3;
+ * and, when asked, g_rays_o[n] = g_out_o[n], g_rays_d[n] = R^T g_out_d[n] (fp32, j = 0, 1, 2 in order, the forward's R).
+ * Reduction over the rays -- no atomics, a fixed order, two calls give the same bits; ids in any order:
+ *   the batch is cut into K = min(NSOS_CAMERA_MAX_CHUNKS, ceil(n_rays / NSOS_CAMERA_CHUNK)) contiguous
+ *   chunks of L = ceil(n_rays / K) rounded up to 256 rays.  One 256-thread workgroup per (camera c, chunk k) scans the chunk's ids:
+ *   thread t takes rays k L + t, + 256, ... ascending and adds the 12 products of its rays with id == c in fp64 (each product of two
+ *   fp32 numbers is exact in fp64); the 64 lanes of a wave are summed in six fixed pairing steps (nsos_wave_sum, every lane
+ *   adding the same pairs): lane l with l ^ 1; with l ^ 2; inside each group of 8 lanes with its mirror 7 - (l % 8) (row_half_mirror);
+ *   inside each row of 16 with its mirror 15 - (l % 16) (row_mirror); row r with row r ^ 1 (lane kept); half with half; the four
+ *   waves as ((v0 + v1) + v2) + v3; partial [c][k][12] goes to the workspace.  A second kernel, one thread per camera, adds the K
+ *   partials k ascending, contracts in fp64 (theta and the normalised quaternion recomputed in fp64 from the fp32 rvec) and rounds
+ *   each output to fp32 once.  Hence camera c's gradient depends only on c's own rays and their POSITIONS in the batch: whatever
+ *   the other rays hold, and whichever other camera they name, changes no bit of it.  A camera without a ray gets exact zeros.
+ * Out-of-range ids (the reference raises an IndexError): nothing outside rvec / tvec is ever read.  A ray whose id is outside
+ * [0, n_cams) gets NaN in out_o and out_d, enters no sum, and gets zeros in g_rays_o / g_rays_d.
+ * workspace: nsos_camera_workspace_bytes(n_rays, n_cams) = 96 n_cams K bytes (0 for n_cams <= 0 or n_rays < 0), 8-byte aligned,
+ * needed only when g_rvec or g_tvec is asked for; contents undefined on return.
+ * Validated before anything is launched: a NULL input or output (backward: each of the four outputs may be NULL, not all of them;
+ * the workspace may be NULL when neither g_rvec nor g_tvec is asked for) -> -1; n_cams <= 0 or n_rays < 0 -> -2; n_rays == 0 -> 0
+ * with no launch; n_cams > NSOS_CAMERA_MAX_CAMS -> -3; a workspace too small -> -4.  Launches only, on `stream`: no host
+ * synchronisation, no allocation: capturable. */
+#define NSOS_CAMERA_CHUNK 2048
+#define NSOS_CAMERA_MAX_CHUNKS 64
+#define NSOS_CAMERA_MAX_CAMS 65535
+size_t nsos_camera_workspace_bytes(int64_t n_rays, int32_t n_cams);
+int32_t nsos_camera_transform(const float* rays_o, const float* rays_d, const int32_t* cam_ids, const float* rvec, const float* tvec,
+                              int64_t n_rays, int32_t n_cams, float* out_o, float* out_d, void* stream);
+int32_t nsos_camera_transform_backward(const float* g_out_o, const float* g_out_d, const float* rays_d, const int32_t* cam_ids,
+                                       const float* rvec, int64_t n_rays, int32_t n_cams, void* workspace, size_t workspace_bytes,
+                                       float* g_rvec, float* g_tvec, float* g_rays_o, float* g_rays_d, void* stream);
 
 #ifdef __cplusplus
 }

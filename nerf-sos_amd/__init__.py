@@ -17,6 +17,8 @@ from . import dino  # noqa: F401
 from .dino import DinoViT  # noqa: F401
 from . import lpips  # noqa: F401
 from .lpips import LPIPS  # noqa: F401
+from . import camera  # noqa: F401
+from .camera import CameraTransformer  # noqa: F401
 from .losses import CorrelationLoss, GeoCorrelationLoss, NeRFContrastive  # noqa: F401
 
-__all__ = ["NeRFNet", "NeRFMLP", "MLP", "export_density", "ops", "sharding", "losses", "io", "synthetic", "quality", "metrics", "CorrelationLoss", "GeoCorrelationLoss", "NeRFContrastive", "GraphedRender", "GraphedPatchStep", "dino", "DinoViT", "lpips", "LPIPS"]
+__all__ = ["NeRFNet", "NeRFMLP", "MLP", "export_density", "ops", "sharding", "losses", "io", "synthetic", "quality", "metrics", "CorrelationLoss", "GeoCorrelationLoss", "NeRFContrastive", "GraphedRender", "GraphedPatchStep", "dino", "DinoViT", "lpips", "LPIPS", "camera", "CameraTransformer"]

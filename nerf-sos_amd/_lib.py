@@ -177,6 +177,9 @@ SIGNATURES = {
     "nsos_lpips_pack": (_i32, [C.POINTER(LpipsTensors), _fp, _sz, _fp]),
     "nsos_lpips_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "nsos_lpips_forward": (_i32, [_fp, _fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
+    "nsos_camera_workspace_bytes": (_sz, [_i64, _i32]),
+    "nsos_camera_transform": (_i32, [_fp, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _fp, _fp]),
+    "nsos_camera_transform_backward": (_i32, [_fp, _fp, _fp, _fp, _fp, _i64, _i32, _fp, _sz, _fp, _fp, _fp, _fp, _fp]),
     "nsos_corr_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "nsos_app_correlation_loss": (_i32, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                          _f32, _f32, _f32, _f32, _fp, _fp, _fp, _sz, _fp]),

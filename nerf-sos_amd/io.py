@@ -174,14 +174,17 @@ class DeviceScene:
         return rays, tgt, msk
 
     def patch_batch(self, image_indices, crop_size: int, patch_stride: int = 1, origins=None,
-                    sel_device: Optional[torch.Tensor] = None) -> dict:
+                    sel_device: Optional[torch.Tensor] = None, cam_id: bool = False) -> dict:
         """B = len(image_indices) items of the reference's PatchNeRFDataset (crop_size = patch_size * patch_stride,
         run_nerf.py:407-408) collated by PatchBatchCollater, in ONE launch:
           rays [B,P*P,2,3] (a view of `rays_planar` [2,B,P,P,3], the layout NeRFNet / sharded_patch_step consume directly:
           the trainer's reshape + permute, engines/trainer.py:63-64, is already done), target_s [B,P*P,3],
           masks [B,P*P,1], poses [B,3,5] or [B,4,4] (= self.poses[i]), start_idx [B,2] float32 -- P = ceil(crop_size / patch_stride).
         `origins`: [(h_idx, w_idx)] per item; None draws them like the reference (`draw_patch_origins`).
-        `sel_device`: int32 [B,3] device tensor of (image, h_idx, w_idx) instead (nothing crosses PCIe; graph capture)."""
+        `sel_device`: int32 [B,3] device tensor of (image, h_idx, w_idx) instead (nothing crosses PCIe; graph capture).
+        `cam_id`: also "cam_ids" [B,P*P] int32, every ray's image index within the split (the reference's `cam_id=True`,
+        data/datasets.py:100,236: what CameraTransformer.transform takes): column 0 of `sel_device` expanded on the device, or the
+        host list `image_indices` uploaded ([B] int32) and expanded there."""
         P = -(-int(crop_size) // int(patch_stride))
         with torch.cuda.device(self.device):
             if sel_device is not None:
@@ -208,15 +211,22 @@ class DeviceScene:
                                                    ops._p(rays[0]), ops._p(rays[1]), ops._p(tgt), ops._p(msk), ops._p(poses),
                                                    ops._p(start), ops._stream()), "nsos_patch_batch")
         out = {"rays": rays.permute(1, 2, 0, 3), "rays_planar": rays.reshape(2, B, P, P, 3), "poses": poses, "start_idx": start}
+        if cam_id:
+            if sel_device is not None:   # clamped like emit_pixel clamps a device descriptor: the id names the image the ray is from
+                img = sel_device[:, 0].clamp(0, self.image_count - 1)
+            else:                        # the host selection (range-checked above) reaches the kernel by value: one small upload
+                img = torch.tensor(idx, dtype=torch.int32).to(self.device)
+            out["cam_ids"] = img[:, None].expand(B, P * P).contiguous()
         if tgt is not None:
             out["target_s"] = tgt
         if msk is not None:
             out["masks"] = msk
         return out
 
-    def pixel_batch(self, pix: torch.Tensor) -> dict:
+    def pixel_batch(self, pix: torch.Tensor, cam_id: bool = False) -> dict:
         """Records of an explicit list of flat pixel indices (image*H + y)*W + x (int64 device tensor, any shape):
-        rays [2, *shape, 3], target_s [*shape, 3], masks [*shape, 1]."""
+        rays [2, *shape, 3], target_s [*shape, 3], masks [*shape, 1]; with `cam_id` also cam_ids [*shape] int32, the pixel's
+        image index (data/datasets.py:166,312), taken from `pix` on the device."""
         if pix.dtype != torch.int64 or not pix.is_cuda:
             raise TypeError("pix must be an int64 GPU tensor of flat pixel indices")
         pix = pix.contiguous()
@@ -225,21 +235,24 @@ class DeviceScene:
             _lib.check(_lib.lib().nsos_pixel_batch(*self._source_args(), ops._p(pix), pix.numel(), ops._p(rays[0]), ops._p(rays[1]),
                                                    ops._p(tgt), ops._p(msk), ops._stream()), "nsos_pixel_batch")
         out = {"rays": rays}
+        if cam_id:
+            img = torch.div(pix, self.height * self.width, rounding_mode="floor")
+            out["cam_ids"] = img.clamp(0, self.image_count - 1).to(torch.int32)     # clamped like pixel_batch_kernel's gather
         if tgt is not None:
             out["target_s"] = tgt
         if msk is not None:
             out["masks"] = msk
         return out
 
-    def ray_batch(self, indices) -> dict:
+    def ray_batch(self, indices, cam_id: bool = False) -> dict:
         """RayNeRFDataset items `indices` of the flattened [N*H*W] training set (data/datasets.py:149-152,159-171) collated by
         RayBatchCollater (data/collater.py:7-29): rays [2,B,3], target_s [B,3], masks [B,1].  `indices`: a host sequence
         (one small upload) or an int64 device tensor (e.g. `torch.randperm(n, device=...)[:B]`: nothing crosses PCIe)."""
         if isinstance(indices, torch.Tensor) and indices.is_cuda:
-            return self.pixel_batch(indices.long())
-        return self.pixel_batch(torch.as_tensor(list(indices), dtype=torch.int64).to(self.device))
+            return self.pixel_batch(indices.long(), cam_id=cam_id)
+        return self.pixel_batch(torch.as_tensor(list(indices), dtype=torch.int64).to(self.device), cam_id=cam_id)
 
-    def view_batch(self, i: int, n_rand: int, precrop_frac: Optional[float] = None) -> dict:
+    def view_batch(self, i: int, n_rand: int, precrop_frac: Optional[float] = None, cam_id: bool = False) -> dict:
         """ViewNeRFDataset.__getitem__(i) (--no_batching; data/datasets.py:272-300) + ViewBatchCollater: `n_rand` pixels of
         view i chosen by `np.random.choice(..., replace=False)` from the whole view, or from the centre crop while
         pre-cropping (`precrop_frac`, :282-289) -- the reference's global numpy generator, same draws after the same seed."""
@@ -252,4 +265,4 @@ class DeviceScene:
             ys, xs = np.arange(H), np.arange(W)
         sel = np.random.choice(len(ys) * len(xs), size=[int(n_rand)], replace=False)                 # :291
         flat = (int(i) * H + ys[sel // len(xs)]) * W + xs[sel % len(xs)]
-        return self.pixel_batch(torch.from_numpy(flat.astype(np.int64)).to(self.device))
+        return self.pixel_batch(torch.from_numpy(flat.astype(np.int64)).to(self.device), cam_id=cam_id)

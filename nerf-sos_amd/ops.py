@@ -486,6 +486,86 @@ def ray_grad_reduce(g_pts: torch.Tensor, g_dirs: Optional[torch.Tensor], z_vals:
     return g_o, g_d
 
 
+# ------------------------------------------------------------------------------------------ camera layer (csrc/camera.hip)
+def _cam_ids(cam_ids, n_cams: int, device) -> torch.Tensor:
+    """Camera ids as a contiguous int32 GPU tensor.  Ids that are on the host (a sequence or a CPU tensor) are range-checked here,
+    like the reference's indexing would, and uploaded; ids already on the device are taken as they are (the kernels give an
+    out-of-range ray NaN outputs and no gradient)."""
+    if isinstance(cam_ids, torch.Tensor) and cam_ids.is_cuda:
+        if cam_ids.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"nerf_sos_amd: `cam_ids` must be an integer tensor, got {cam_ids.dtype}")
+        if cam_ids.dtype == torch.int64:      # compared in the wide type, then narrowed: 2^32 must not wrap to camera 0
+            cam_ids = torch.where((cam_ids >= 0) & (cam_ids < n_cams), cam_ids, -1).to(torch.int32)
+        return cam_ids.contiguous()
+    host = torch.as_tensor(cam_ids)
+    if host.dtype.is_floating_point or host.dtype == torch.bool:
+        raise TypeError(f"nerf_sos_amd: `cam_ids` must be integers, got {host.dtype}")
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= n_cams):
+        raise IndexError(f"camera id outside [0, {n_cams}): {int(host.min())} .. {int(host.max())}")
+    return host.to(torch.int32).contiguous().to(device)
+
+
+def camera_workspace_bytes(n_rays: int, n_cams: int) -> int:
+    return int(_lib.lib().nsos_camera_workspace_bytes(int(n_rays), int(n_cams)))
+
+
+def camera_workspace(n_rays: int, n_cams: int, device) -> torch.Tensor:
+    """The workspace nsos_camera_transform_backward needs for the parameter gradients (fp64 partial sums)."""
+    n = camera_workspace_bytes(n_rays, n_cams)
+    return torch.empty((n + 7) // 8, device=device, dtype=torch.float64)
+
+
+def camera_transform(rays_o: torch.Tensor, rays_d: torch.Tensor, cam_ids, rvec: torch.Tensor, tvec: torch.Tensor,
+                     planar: bool = False, ids_ready: bool = False):
+    """CameraTransformer.forward (models/camera.py:120-143; nsos_camera_transform): rays_o, rays_d [...,3], cam_ids [...] integers,
+    rvec [C,4] (x, y, z, w), tvec [C,3] -> (rays_o + tvec[id], R(rvec[id]) rays_d), the inputs' shape; planar=True returns the
+    two as one [2,...,3] tensor (the layout NeRFNet takes)."""
+    rays_o, rays_d, rvec, tvec = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d"), _dev(rvec, "rvec"), _dev(tvec, "tvec")
+    n_cams = int(rvec.shape[0])
+    if rvec.shape != (n_cams, 4) or tvec.shape != (n_cams, 3):
+        raise ValueError(f"rvec must be [C,4] and tvec [C,3], got {tuple(rvec.shape)} and {tuple(tvec.shape)}")
+    ids = cam_ids if ids_ready else _cam_ids(cam_ids, n_cams, rays_o.device)   # ids_ready: already through _cam_ids (camera.py)
+    if rays_o.shape != rays_d.shape or rays_o.shape[-1] != 3 or tuple(ids.shape) != tuple(rays_o.shape[:-1]):
+        raise ValueError(f"rays_o / rays_d must be [...,3] and cam_ids [...], got {tuple(rays_o.shape)}, {tuple(rays_d.shape)}, {tuple(ids.shape)}")
+    with torch.cuda.device(rays_o.device):
+        out = torch.empty((2,) + tuple(rays_o.shape), device=rays_o.device, dtype=torch.float32)
+        out_o, out_d = out[0], out[1]
+        _lib.check(_lib.lib().nsos_camera_transform(_p(rays_o), _p(rays_d), _p(ids), _p(rvec), _p(tvec), ids.numel(), n_cams,
+                                                    _p(out_o), _p(out_d), _stream()), "nsos_camera_transform")
+    return out if planar else (out_o, out_d)
+
+
+def camera_transform_backward(g_out_o: torch.Tensor, g_out_d: torch.Tensor, rays_d: torch.Tensor, cam_ids, rvec: torch.Tensor,
+                              workspace: Optional[torch.Tensor] = None, params: bool = True, rays: bool = False,
+                              ids_ready: bool = False):
+    """(g_rvec [C,4], g_tvec [C,3], g_rays_o, g_rays_d) of camera_transform (nsos_camera_transform_backward); the parameter pair
+    is None unless `params`, the ray pair None unless `rays`.  `workspace`: camera_workspace(n_rays, C) or larger (allocated here
+    when None)."""
+    g_out_o, g_out_d, rays_d, rvec = _dev(g_out_o, "g_out_o"), _dev(g_out_d, "g_out_d"), _dev(rays_d, "rays_d"), _dev(rvec, "rvec")
+    n_cams = int(rvec.shape[0])
+    ids = cam_ids if ids_ready else _cam_ids(cam_ids, n_cams, rays_d.device)
+    if g_out_o.shape != rays_d.shape or g_out_d.shape != rays_d.shape or tuple(ids.shape) != tuple(rays_d.shape[:-1]):
+        raise ValueError("camera_transform_backward: g_out_o, g_out_d and rays_d must share the shape [...,3] of cam_ids [...]")
+    if not (params or rays):
+        return None, None, None, None
+    dev = rays_d.device
+    with torch.cuda.device(dev):
+        g_rvec = torch.empty((n_cams, 4), device=dev, dtype=torch.float32) if params else None
+        g_tvec = torch.empty((n_cams, 3), device=dev, dtype=torch.float32) if params else None
+        g_o = torch.empty_like(rays_d) if rays else None
+        g_d = torch.empty_like(rays_d) if rays else None
+        if params and workspace is None:
+            workspace = camera_workspace(ids.numel(), n_cams, dev)
+        ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+        if ids.numel() == 0 and params:
+            g_rvec.zero_()
+            g_tvec.zero_()
+        _lib.check(_lib.lib().nsos_camera_transform_backward(_p(g_out_o), _p(g_out_d), _p(rays_d), _p(ids), _p(rvec), ids.numel(), n_cams,
+                                                             _p(workspace) if params else None, ws_bytes if params else 0, _p(g_rvec),
+                                                             _p(g_tvec), _p(g_o), _p(g_d), _stream()), "nsos_camera_transform_backward")
+    return g_rvec, g_tvec, g_o, g_d
+
+
 def mlp_generic_forward_points(plan: GenericPlan, packed: torch.Tensor, pts: torch.Tensor, dirs: Optional[torch.Tensor]) -> torch.Tensor:
     """raw [P,C] for explicit points (and per-point view directions, if the net takes them)."""
     pts = _dev(pts, "pts")

@@ -59,6 +59,28 @@ def synthetic_patches(n_patches: int, patch: int = 64, stride: int = 6, seed: in
     return full[:, pix.to(full.device)].reshape(2, n_patches, patch, patch, 3).contiguous()
 
 
+def corrupt_cameras(cam_poses, offset=(-0.1, 0.1), rotation=(-5, 5)):
+    """models/camera.py:6-40, host numpy: every pose [N, 3 or 4, >=4] gets a uniform offset in `offset` per axis and is rotated by
+    Rx Ry Rz of uniform Euler angles in `rotation` (degrees) -> [N,3,4].  The reference's global numpy generator and its order of
+    draws (offsets, then angles), so the same poses come out after the same `np.random.seed`: what a CameraTransformer is trained
+    to undo."""
+    import numpy as np
+    n = cam_poses.shape[0]
+    rand_t = np.random.rand(n, 3)
+    perturb_t = (1 - rand_t) * offset[0] + rand_t * offset[1]
+    tr = (cam_poses[:, :3, 3] + perturb_t)[..., None]                              # [N,3,1]
+    rand_r = np.random.rand(n, 3)
+    ang = np.deg2rad((1 - rand_r) * rotation[0] + rand_r * rotation[1])
+    cos, sin, one, zero = np.cos(ang), np.sin(ang), np.ones(n), np.zeros(n)
+    Rx = np.stack((one, zero, zero, zero, cos[:, 0], -sin[:, 0], zero, sin[:, 0], cos[:, 0]), axis=1).reshape(-1, 3, 3)
+    Ry = np.stack((cos[:, 1], zero, sin[:, 1], zero, one, zero, -sin[:, 1], zero, cos[:, 1]), axis=1).reshape(-1, 3, 3)
+    Rz = np.stack((cos[:, 2], -sin[:, 2], zero, sin[:, 2], cos[:, 2], zero, zero, zero, one), axis=1).reshape(-1, 3, 3)
+    rot = cam_poses[:, :3, :3]
+    for perturb_r in (Rz, Ry, Rx):                                                 # camera.py:37-38
+        rot = np.matmul(perturb_r, rot)
+    return np.concatenate([rot, tr], axis=-1)
+
+
 def spiky_density_(net, gain: float = 40.0, shift: float = -1.5):
     """In place: scale the sigma heads of a (random-init) NeRFNet so that a few samples per ray carry almost all the
     weight -- the regime trained scenes are in, and the one that exercises the hierarchical sampler's search and the

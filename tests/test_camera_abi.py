@@ -1,0 +1,157 @@
+"""CPU: the camera layer's C ABI (nsos_camera_*: bound, validated before any launch), the CameraTransformer module's reference
+surface (names, shapes, initial values, buffers vs parameters, the reference's state dict), the host helper corrupt_cameras, and the
+torch restatement the GPU tests measure against -- all pinned to tests/golden/camera.npz (make_goldens_camera.py, the REAL
+models/camera.py)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import nerf_sos_amd
+from nerf_sos_amd import _lib, ops, synthetic
+import camera_port as cp
+
+NULL, SHAPE, UNSUPPORTED, SMALL = -1, -2, -3, -4
+LAYER_CASES = ("n1_c1", "n63_c3_runs", "n64_c3_empty", "n64_c70_random", "n257_c3_one", "n257_c70_random", "n257_c3_farnorm",
+               "n4099_c3_runs", "n4099_c70_random")
+
+
+def test_camera_symbols_are_bound_and_the_abi_version_stands():
+    lib = _lib.lib()
+    for name in ("nsos_camera_workspace_bytes", "nsos_camera_transform", "nsos_camera_transform_backward"):
+        assert name in _lib.SIGNATURES and hasattr(lib, name), name
+        fn = getattr(lib, name)
+        assert fn.restype is _lib.SIGNATURES[name][0] and list(fn.argtypes) == _lib.SIGNATURES[name][1]
+    assert lib.nsos_abi_version() == 10 == _lib.ABI_VERSION          # added entry points only: nothing existing moved
+
+
+def test_camera_entry_points_validate_before_any_launch():
+    """Host addresses stand in for device pointers: nothing may dereference them, nothing is launched."""
+    lib = _lib.lib()
+    buf = (C.c_double * 8)()
+    p = C.cast(buf, C.c_void_p)
+    big = 1 << 30
+    fwd, bwd = lib.nsos_camera_transform, lib.nsos_camera_transform_backward
+    #   rays_o, rays_d, cam_ids, rvec, tvec, n_rays, n_cams, out_o, out_d, stream
+    ok = [p, p, p, p, p, 8, 3, p, p, None]
+    for i in (0, 1, 2, 3, 4, 7, 8):
+        assert fwd(*[None if j == i else a for j, a in enumerate(ok)]) == NULL, i
+    assert fwd(p, p, p, p, p, 8, 0, p, p, None) == SHAPE and fwd(p, p, p, p, p, 8, -1, p, p, None) == SHAPE
+    assert fwd(p, p, p, p, p, -1, 3, p, p, None) == SHAPE
+    assert fwd(p, p, p, p, p, 0, 3, p, p, None) == 0 and fwd(None, None, None, None, None, 0, 3, None, None, None) == 0   # empty batch
+    assert fwd(p, p, p, p, p, 8, 65536, p, p, None) == UNSUPPORTED
+    #   g_out_o, g_out_d, rays_d, cam_ids, rvec, n_rays, n_cams, workspace, workspace_bytes, g_rvec, g_tvec, g_rays_o, g_rays_d, stream
+    ok = [p, p, p, p, p, 8, 3, p, big, p, p, p, p, None]
+    for i in (0, 1, 2, 3, 4, 7):
+        assert bwd(*[None if j == i else a for j, a in enumerate(ok)]) == NULL, i
+    assert bwd(p, p, p, p, p, 8, 3, p, big, None, None, None, None, None) == NULL                  # nothing asked for
+    assert bwd(p, p, p, p, p, 8, 0, p, big, p, p, p, p, None) == SHAPE and bwd(p, p, p, p, p, -1, 3, p, big, p, p, p, p, None) == SHAPE
+    assert bwd(p, p, p, p, p, 0, 3, p, big, p, p, p, p, None) == 0
+    assert bwd(None, None, None, None, None, 0, 3, None, 0, None, None, None, None, None) == 0
+    assert bwd(p, p, p, p, p, 8, 65536, p, big, p, p, p, p, None) == UNSUPPORTED
+    need = lib.nsos_camera_workspace_bytes(8, 3)
+    assert need > 0
+    assert bwd(p, p, p, p, p, 8, 3, p, need - 1, p, p, p, p, None) == SMALL
+    assert bwd(p, p, p, p, p, 8, 3, p, need - 1, None, p, None, None, None) == SMALL               # g_tvec alone needs it too
+    need = lib.nsos_camera_workspace_bytes(1 << 20, 200)
+    assert bwd(p, p, p, p, p, 1 << 20, 200, p, need - 1, p, p, None, None, None) == SMALL
+
+
+def test_camera_workspace_formula():
+    lib = _lib.lib()
+    w = lib.nsos_camera_workspace_bytes
+    assert w(1, 1) == 96 and w(2048, 1) == 96 and w(2049, 1) == 192 and w(4099, 70) == 3 * 70 * 96   # 12 fp64 sums per (camera, chunk)
+    assert w(1 << 24, 1) == 64 * 96                                                                  # at most 64 chunks
+    assert w(-1, 3) == 0 and w(8, 0) == 0 and w(8, -2) == 0
+    sizes = [0, 1, 63, 64, 2048, 2049, 4099, 65536, 131073, 756 * 1008, 1 << 24]
+    for c in (1, 3, 70, 200):
+        row = [w(n, c) for n in sizes]
+        assert all(a <= b for a, b in zip(row, row[1:])) and row[0] > 0 and row[-1] > row[0]        # monotone in n_rays
+    for n in sizes:
+        col = [w(n, c) for c in (1, 2, 3, 70, 200, 65535)]
+        assert all(a < b for a, b in zip(col, col[1:]))                                              # ... and in n_cams
+    assert ops.camera_workspace_bytes(4099, 70) == w(4099, 70)
+
+
+def test_camera_transformer_mirrors_the_reference_module(golden):
+    g = golden("camera")
+    assert nerf_sos_amd.CameraTransformer is nerf_sos_amd.camera.CameraTransformer
+    for trainable in (False, True):
+        cam = nerf_sos_amd.CameraTransformer(5, trainable=trainable)
+        sd = cam.state_dict()
+        assert list(sd.keys()) == [str(k) for k in g["state__keys"]] == ["rvec", "tvec"]
+        assert sd["rvec"].shape == (5, 4) and sd["tvec"].shape == (5, 3) and sd["rvec"].dtype == torch.float32
+        assert torch.equal(sd["rvec"], torch.tensor([0., 0., 0., 1.]).repeat(5, 1)) and torch.equal(sd["tvec"], torch.zeros(5, 3))
+        names = [n for n, _ in cam.named_parameters()]
+        assert names == (["rvec", "tvec"] if trainable else [])
+        assert [n for n, _ in cam.named_buffers()] == ([] if trainable else ["rvec", "tvec"])
+        assert cam.rvec.requires_grad == trainable and cam.trainable == trainable
+        # the REAL module's state dict loads, strictly
+        cam.load_state_dict({k: torch.from_numpy(g[f"state__{k}"]) for k in ("rvec", "tvec")}, strict=True)
+        assert np.array_equal(cam.rvec.detach().numpy(), g["state__rvec"]) and np.array_equal(cam.tvec.detach().numpy(), g["state__tvec"])
+
+
+def test_camera_has_no_cpu_path():
+    cam = nerf_sos_amd.CameraTransformer(2, trainable=True)
+    o4, d4 = torch.zeros(6, 4), torch.zeros(6, 4)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        cam(o4, d4)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        cam.transform(torch.zeros(2, 6, 3), torch.zeros(6, dtype=torch.int32))
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        cam.rot_mats()
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        ops.camera_transform(torch.zeros(6, 3), torch.zeros(6, 3), [0] * 6, torch.zeros(2, 4), torch.zeros(2, 3))
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        ops.camera_transform_backward(torch.zeros(6, 3), torch.zeros(6, 3), torch.zeros(6, 3), [0] * 6, torch.zeros(2, 4))
+    with pytest.raises(ValueError):
+        cam(torch.zeros(6, 3), torch.zeros(6, 3))                    # the reference's format carries the id column
+    with pytest.raises(ValueError):
+        cam.transform(torch.zeros(6, 3), torch.zeros(6, dtype=torch.int32))
+
+
+def test_host_camera_ids_are_range_checked():
+    """Ids that are on the host are checked before anything is uploaded or launched (the reference's indexing raises too)."""
+    for bad in ([0, 1, 2], [-1, 0, 0], torch.tensor([0, 5, 1])):
+        with pytest.raises(IndexError):
+            ops._cam_ids(bad, 2, "cpu")
+    with pytest.raises(TypeError):
+        ops._cam_ids([0.0, 1.0], 2, "cpu")
+    assert ops._cam_ids([1, 0, 1], 2, "cpu").dtype == torch.int32
+
+
+def test_corrupt_cameras_equals_the_reference_function(golden):
+    g = golden("camera")
+    poses = g["corrupt__poses"]
+    np.random.seed(0)
+    a = synthetic.corrupt_cameras(poses)
+    b = synthetic.corrupt_cameras(poses, offset=(-0.3, 0.2), rotation=(-10, 20))
+    assert a.shape == (6, 3, 4) and a.dtype == g["corrupt__default"].dtype
+    assert np.array_equal(a, g["corrupt__default"]) and np.array_equal(b, g["corrupt__wide"])
+    assert not np.array_equal(a[:, :, :3], poses[:, :, :3])
+
+
+@pytest.mark.parametrize("name", LAYER_CASES)
+def test_camera_port_fp32_equals_the_reference_bit_for_bit(golden, name):
+    g = golden("camera")
+    ids = torch.from_numpy(g[f"{name}__ids"])
+    n = ids.numel()
+    pool = [torch.from_numpy(g[f"pool__{k}"][:n]) for k in ("rays_o", "rays_d", "G_o", "G_d")]
+    rvec, tvec = torch.from_numpy(g[f"{name}__rvec"]), torch.from_numpy(g[f"{name}__tvec"])
+    torch.use_deterministic_algorithms(True)
+    try:
+        got = cp.grads(pool[0], pool[1], ids, rvec, tvec, pool[2], pool[3])
+    finally:
+        torch.use_deterministic_algorithms(False)
+    # (deterministic algorithms: the index backward then accumulates camera by camera in ray order, whatever the thread count)
+    for k in ("out_o", "out_d", "g_rays_d", "g_rvec", "g_tvec"):
+        assert np.array_equal(got[k].numpy(), g[f"{name}__ref32__{k}"]), k
+    assert torch.equal(got["g_rays_o"], pool[2])
+    # the fixture's fp64 side is the port in fp64
+    got64 = cp.grads(pool[0].double(), pool[1].double(), ids, rvec.double(), tvec.double(), pool[2].double(), pool[3].double())
+    for k in ("g_rvec", "g_tvec"):
+        assert np.abs(got64[k].numpy() - g[f"{name}__ref64__{k}"]).max() <= 1e-12 * np.abs(g[f"{name}__ref64__{k}"]).max()
+    for k in ("out_d", "g_rays_d"):
+        want = g[f"{name}__ref32__{k}"].astype(np.float64) + g[f"{name}__res64__{k}"].astype(np.float64)
+        assert np.abs(got64[k].numpy() - want).max() <= 1e-12 * np.abs(want).max()

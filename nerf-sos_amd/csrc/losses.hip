@@ -37,7 +37,7 @@ struct CorrParams {
 struct Ws {
     double* rowsum;    // [2][B][N]
     double* partial;   // [2][kRedBlocks]  scratch for block partials
-    double* scal;      // [16]: 0,1 sum fd (neg,self)  2,3 sum fd1  4,5 loss sums  6 depth max (as double)
+    double* scal;      // [16]: 0,1 sum fd (neg,self)  2,3 sum fd1  4,5 loss sums  6 depth max (as double)  7 NaN flag (geo)  8.. spare
     float* pts;        // geo: xyz [B][N][4]           app: unused
     float* cn;         // normalised codes, row side    [B][N][kMaxC]
     float* cn2;        // app only: column-side codes of the negative set [B][N][kMaxC]
@@ -143,10 +143,8 @@ __global__ __launch_bounds__(256) void depth_max_kernel(const float* __restrict_
     if (threadIdx.x == 0) {
         for (int i = 1; i < (int)(blockDim.x >> 6); ++i) m = sm[i] > m ? sm[i] : m;
         partial[blockIdx.x] = m;
-        if (blockIdx.x == 0) {
-            scal[7] = 0.0;  // set by geo_prep_kernel when a point's depth / ray / code holds a NaN: the loss is NaN then, as the reference's is
-            scal[8] = 0.0;  // the last-arriver tickets of the pair passes (nsos_last_block: two 32-bit counters)
-        }
+        // set by geo_prep_kernel when a point's depth / ray / code holds a NaN: the loss is NaN then, as the reference's is
+        if (blockIdx.x == 0) scal[7] = 0.0;
     }
 }
 // the maximum over depth_max_kernel's block partials (nb <= 256 = the block size of its callers), valid in every thread: what
@@ -162,34 +160,6 @@ __device__ __forceinline__ double depth_max_of(const double* __restrict__ partia
     m = dm[0];
     for (int i = 1; i < (int)(blockDim.x >> 6); ++i) m = dm[i] > m ? dm[i] : m;
     return m;
-}
-
-// Exactly ONE workgroup of a grid of `total` gets true (in all its threads): the one that arrives last -- every other workgroup's
-// global writes made before its call are visible to it (agent-scope release by each arriver, acquire by the last).  The ticket
-// resets itself for the next launch.  Folds a reduction's finishing step into the kernel that produced the partials: a launch of
-// its own costs ~4.8 us on the step's critical path (profiles/r05/h_c3_step_timeline.txt), seven of them per training step.
-// Round 6, second form (the first one released with __threadfence(): buffer_wbl2 + buffer_inv per workgroup, 66-196 us per step
-// slower than the launches it saved, profiles/r06/e_loss_finish_fold_ab.txt): NO cache-wide fence.  What the last workgroup reads --
-// the block partials and the row sums -- is written with agent-scope (sc1, write-through) stores and read with agent-scope loads
-// (dev_store / dev_load below), so only those few kilobytes travel through memory; "s_waitcnt vmcnt(0)" before the ticket makes each
-// wave's own stores complete first, and the ticket itself is a device-scope atomic.
-__device__ __forceinline__ void dev_store(double* p, double v) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double dev_load(const double* p) {
-    return __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ bool nsos_last_block(unsigned* ticket, unsigned total) {
-    __shared__ int last_s;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_s = t == total - 1u;
-        if (last_s) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    return last_s != 0;
 }
 
 // How a kernel finds the inputs of patch n of a (possibly stacked) batch.  The training step scores TWO semantic maps (coarse
@@ -273,14 +243,6 @@ struct PairArgs {
     int n_rows;
     float* gcolp;          // geo, fused pass 3: column-gradient partials [2][row slots][row blocks][C][N]
     int Bg;                // geo: geometry patches behind the B code patches (patch n -> geometry n % Bg); 0 = B
-    // single-process calls (round 6): the passes' finishing reductions run in the LAST workgroup of the pass itself (nsos_last_block)
-    // instead of in launches of their own.  tickets = two zeroed 32-bit counters (workspace scal[8]), nb = block partials per set.
-    unsigned* tickets;     // NULL: finish kernels are launched (the row-partitioned multi-GPU phases)
-    int nb;
-    double cnt;            // pass 3: B N N
-    float* loss;           // pass 3: where the loss goes
-    const double* flags;   // pass 3, geo: scal of the workspace ([7] = NaN flag)
-    int geo;
 };
 
 __device__ __forceinline__ int row_patch(const PairArgs& A) { return A.rows ? A.rows[blockIdx.y] : (int)blockIdx.y; }
@@ -308,7 +270,8 @@ __device__ __forceinline__ const float* col_codes(const PairArgs& A, int set, in
     return (set == 0 ? A.cn2 : A.cn) + (size_t)n * A.N * kMaxC;
 }
 
-// PASS 1: row sums.  PASS 3: loss + row-code gradient.  (PASS 2, sum fl32(fd - rowmean), is no longer launched: rowmean_residual_kernel.)
+// PASS 1: row sums.  PASS 3: loss + row-code gradient.  (There is no PASS 2 here: sum fl32(fd - rowmean) comes from the row sums,
+// rowmean_residual_kernel.)
 // GEO: a workgroup = kRows row points x kSlabs column slabs, 1024 threads = four waves per SIMD (thread (row, slab) loops over
 // the slab's N / kSlabs columns); the slabs' fp64 partials are folded in slab order through LDS -- the dynamic region, reused
 // once every wave is done with the column image.  The column image (up to 144 KiB) allows ONE workgroup per CU, so the
@@ -378,11 +341,9 @@ __device__ __forceinline__ int col_of_lane(unsigned lane) {
 // over all N^2 pairs (pair_cols_kernel: 88 of the 220 us the geometric loss took per C3 step) by ~4 VALU per pair here.
 __host__ __device__ inline int pair_padded_columns(int N, int slabs) { return ((N + slabs * 32 - 1) / (slabs * 32)) * 32 * slabs; }
 
-__device__ __forceinline__ void pass1_finish_in_block(const PairArgs& A, double* red);
-__device__ __forceinline__ void pass3_finish_in_block(const PairArgs& A);
-
 template <bool GEO, int C, int PASS, bool NARROW = false, bool FUSE = false>
 __global__ __launch_bounds__((PairShape<GEO, NARROW>::kThreads)) void pair_rows_kernel(const PairArgs A) {
+    static_assert(PASS == 1 || PASS == 3, "passes 2 and 4 are kernels of their own");
     static_assert(!FUSE || (GEO && PASS == 3 && !NARROW), "the fused column gradient needs 64-row waves of the geometric pass 3");
     extern __shared__ __attribute__((aligned(16))) float lds[];   // columns: GEO xyz [N][4] then codes [N][kMaxC]
     __shared__ double red[4];
@@ -418,8 +379,10 @@ __global__ __launch_bounds__((PairShape<GEO, NARROW>::kThreads)) void pair_rows_
     const float* fdrow = GEO ? nullptr : A.fdmat + (((size_t)set * A.B + n) * N + pc) * N;
     const double cnt = (double)A.B * N * N;
     float rm = 0.0f, m1 = 0.0f, old_mean = 0.0f;
-    if (PASS >= 2) rm = (float)(A.rowsum[((size_t)set * A.B + n) * N + pc] / (double)N);   // fd.mean([3,4]), :318
-    if (PASS == 3) { old_mean = (float)(A.scal[set] / cnt); m1 = (float)(A.scal[2 + set] / cnt); }
+    if (PASS == 3) {
+        rm = (float)(A.rowsum[((size_t)set * A.B + n) * N + pc] / (double)N);   // fd.mean([3,4]), :318
+        old_mean = (float)(A.scal[set] / cnt); m1 = (float)(A.scal[2 + set] / cnt);
+    }
     const float shift = set == 0 ? A.prm.neg_shift : A.prm.self_shift;
     const float gscale = -(set == 0 ? A.prm.neg_weight : A.prm.self_weight) / (float)cnt;
     // sums: fp32 over blocks of kBlk consecutive q (fixed order), blocks folded into fp64
@@ -485,7 +448,6 @@ __global__ __launch_bounds__((PairShape<GEO, NARROW>::kThreads)) void pair_rows_
             const float fd = GEO ? inv_l1<3>(x, lx + q * 4, A.max_depth) : fdrow[q];
             if (PASS == 1) { acc32 += fd; continue; }
             const float fd1 = fd - rm;                         // fd -= fd.mean([3,4]), :318
-            if (PASS == 2) { acc32 += fd1; continue; }
             const float fd2 = (fd1 - m1) + old_mean;           // fd - fd.mean() + old_mean, :319
             const float t = fd2 - shift;
             if constexpr (GEO) {
@@ -525,30 +487,12 @@ __global__ __launch_bounds__((PairShape<GEO, NARROW>::kThreads)) void pair_rows_
             }
     }
     const bool owner = live && sl == 0;
-    if (PASS == 1 && owner) {
-        if (A.tickets) dev_store(&A.rowsum[((size_t)set * A.B + n) * N + p], acc);     // (read by this launch's last workgroup)
-        else A.rowsum[((size_t)set * A.B + n) * N + p] = acc;
-    }
+    if (PASS == 1 && owner) A.rowsum[((size_t)set * A.B + n) * N + p] = acc;
     if (PASS == 3 && owner)
 #pragma unroll
         for (int c = 0; c < kMaxC; ++c) A.grow[(((size_t)set * A.B + n) * N + p) * kMaxC + c] = c < C ? (float)g[c] : 0.0f;
     const double s = block_sum(owner ? acc : 0.0, red);
-    if (threadIdx.x == 0) {
-        if (A.tickets) dev_store(&A.partial[(size_t)set * kRedBlocks + blockIdx.y * gridDim.x + blockIdx.x], s);
-        else A.partial[(size_t)set * kRedBlocks + blockIdx.y * gridDim.x + blockIdx.x] = s;
-    }
-    // single-process calls: the pass's finishing reduction in its last workgroup (PASS 1 of a stacked geometric batch finishes in
-    // pair_rowsum_copy_kernel instead, which runs between the two)
-    if (A.tickets != nullptr && (PASS == 3 || !(GEO && A.Bg > 0 && A.Bg < A.B))) {
-        if (nsos_last_block(A.tickets + (PASS == 1 ? 0 : 1), gridDim.x * gridDim.y * gridDim.z)) {
-            if constexpr (PASS == 1) {
-                __shared__ double fin[16];
-                pass1_finish_in_block(A, fin);
-            } else {
-                pass3_finish_in_block(A);
-            }
-        }
-    }
+    if (threadIdx.x == 0) A.partial[(size_t)set * kRedBlocks + blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void pair_rowsum_copy_kernel(const PairArgs A, int row_blocks) {
@@ -561,23 +505,6 @@ __global__ __launch_bounds__(256) void pair_rowsum_copy_kernel(const PairArgs A,
     if (blockIdx.x == 0)
         for (int k = threadIdx.x; k < row_blocks; k += blockDim.x)
             A.partial[(size_t)set * kRedBlocks + blockIdx.y * row_blocks + k] = A.partial[(size_t)cset * kRedBlocks + cslot * row_blocks + k];
-}
-// the same with pass 1's finishing reduction in the last workgroup (single-process calls; blocks that copy nothing take part too)
-__global__ __launch_bounds__(256) void pair_rowsum_copy_finish_kernel(const PairArgs A, int row_blocks) {
-    int cset, cslot;
-    const int set = blockIdx.z, N = A.N;
-    if (first_with_same_geometry(A, set, blockIdx.y, &cset, &cslot)) {
-        const int n = row_patch(A), cn = A.rows ? A.rows[cslot] : cslot;
-        const int p = blockIdx.x * blockDim.x + threadIdx.x;
-        if (p < N) dev_store(&A.rowsum[((size_t)set * A.B + n) * N + p], A.rowsum[((size_t)cset * A.B + cn) * N + p]);
-        if (blockIdx.x == 0)
-            for (int k = threadIdx.x; k < row_blocks; k += blockDim.x)
-                dev_store(&A.partial[(size_t)set * kRedBlocks + blockIdx.y * row_blocks + k], A.partial[(size_t)cset * kRedBlocks + cslot * row_blocks + k]);
-    }
-    if (nsos_last_block(A.tickets, gridDim.x * gridDim.y * gridDim.z)) {
-        __shared__ double fin[16];
-        pass1_finish_in_block(A, fin);
-    }
 }
 
 // What used to be PASS 2: scal[2 + set] = sum over the evaluated pairs of (fd - rowmean), the numerator of the mean the
@@ -613,56 +540,6 @@ __global__ void pair_finish_kernel(const double* __restrict__ partial, int nb, d
     const double s = partial_sum(partial, nb, blockIdx.x);
     if (threadIdx.x == 0) scal[slot + blockIdx.x] = s;
 }
-// The same two finishing steps as device functions for the LAST workgroup of a pass (any block size that is a multiple of 64):
-// identical summation orders, so the folded and the launched forms give the same bits.
-// partial_sum with agent-scope loads (the partials were written by other workgroups of the SAME launch)
-__device__ __forceinline__ double partial_sum_dev(const double* __restrict__ partial, int nb, int set) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nb; i += 64) s += dev_load(&partial[(size_t)set * kRedBlocks + i]);
-    return nsos_wave_sum(s);
-}
-__device__ __forceinline__ void pass1_finish_in_block(const PairArgs& A, double* red /* [16] */) {
-    for (int set = 0; set < 2; ++set) {
-        if (threadIdx.x < 64) {
-            const double s = partial_sum_dev(A.partial, A.nb, set);
-            if (threadIdx.x == 0) A.scal[set] = s;
-        }
-        // rowmean_residual_sum strides by blockDim.x: pass1_finish_kernel runs it with 1024 threads -- keep that order
-        double r = 0.0;
-        {
-            const int N = A.N, nr = A.rows ? A.n_rows : A.B;
-            for (int v = threadIdx.x; v < 1024; v += blockDim.x) {          // virtual thread v of the 1024-thread form
-                double sv = 0.0;
-                for (long long k = v; k < (long long)nr * N; k += 1024) {
-                    const int n = A.rows ? A.rows[k / N] : (int)(k / N), p = (int)(k % N);
-                    const double rs = dev_load(&A.rowsum[((size_t)set * A.B + n) * N + p]);
-                    const float rm = (float)(rs / (double)N);
-                    sv += rs - (double)N * (double)rm;
-                }
-                // fold the virtual wave (64 consecutive virtual threads = this wave's lanes) exactly as block_sum does
-                sv = nsos_wave_sum(sv);
-                if ((threadIdx.x & 63) == 0) red[v >> 6] = sv;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int i = 0; i < 16; ++i) r += red[i];
-            A.scal[2 + set] = r;
-        }
-        __syncthreads();
-    }
-}
-__device__ __forceinline__ void pass3_finish_in_block(const PairArgs& A) {
-    if (threadIdx.x >= 64) return;
-    const double s0 = partial_sum_dev(A.partial, A.nb, 0), s1 = partial_sum_dev(A.partial, A.nb, 1);
-    if (threadIdx.x != 0) return;
-    A.scal[4] = s0;
-    A.scal[5] = s1;
-    const float l_neg = (float)(s0 / A.cnt), l_self = (float)(s1 / A.cnt);
-    A.loss[0] = A.prm.neg_weight * l_neg + A.prm.self_weight * l_self;
-    if (A.geo && A.flags[7] != 0.0) A.loss[0] = __builtin_nanf("");
-}
-
 // single-process call: what follows pass 1 in ONE launch (block = set): scal[set] = sum of the pass's block partials (wave 0,
 // the same order as pair_finish_kernel) and scal[2 + set] = the row-mean residual (all 1024 threads)
 __global__ __launch_bounds__(1024) void pass1_finish_kernel(const PairArgs A, int nb) {
@@ -920,9 +797,8 @@ __global__ __launch_bounds__(128) void app_sample_kernel(const float* __restrict
                                                          const float* __restrict__ rnd2, int B, int Cf, int Hf, int Wf, int Hc,
                                                          int Wc, int S, float* __restrict__ fn, float* __restrict__ cn,
                                                          float* __restrict__ cn2, float* __restrict__ dinv, float* __restrict__ dinv2,
-                                                         int channel_last, const int* __restrict__ rows, double* __restrict__ scal) {
+                                                         int channel_last, const int* __restrict__ rows) {
     __shared__ double red[2];
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) scal[8] = 0.0;   // the pair passes' last-arriver tickets
     const int p = blockIdx.x, n = rows ? rows[blockIdx.y] : (int)blockIdx.y, side = blockIdx.z, N = S * S;
     const int src = side == 0 ? n : (int)neg[n];
     float gx, gy;
@@ -1083,8 +959,7 @@ __global__ __launch_bounds__(256) void app_scatter_kernel(int B, int N, int S, i
 
 // ------------------------------------------------------------------------------------------ host side
 template <bool GEO, int C, bool NARROW>
-int32_t run_pair_passes_shape(const PairArgs& A_in, bool want_grad, float* loss, hipStream_t st, int phases, const double* flags) {
-    PairArgs A = A_in;
+int32_t run_pair_passes_shape(const PairArgs& A, bool want_grad, float* loss, hipStream_t st, int phases, const double* flags) {
     const int N = A.N, B = A.B;
     const int tb = PairShape<GEO, NARROW>::kThreads, rows_per_block = PairShape<GEO, NARROW>::kRows;
     const dim3 grid((N + rows_per_block - 1) / rows_per_block, A.rows ? A.n_rows : B, 2);
@@ -1115,29 +990,11 @@ int32_t run_pair_passes_shape(const PairArgs& A_in, bool want_grad, float* loss,
     // phases (bit mask): 1 = pass 1, 2 = pass 2, 4 = passes 3 (+4).  A single-process call runs all of them; the row-partitioned
     // multi-GPU call runs them one at a time and all-reduces scal[0..1], scal[2..3] over the ranks in between (the global
     // means of fd and fd1 couple every patch of the batch, utils/image.py:316-319).
-    // single-process call (all phases, a loss to write): fold the finishing reductions into the passes' last workgroups
-    // MEASURED, NOT KEPT AS THE DEFAULT (round 6, profiles/r06/e_loss_finish_fold_ab.txt).  First form (__threadfence() per
-    // workgroup): the replayed C3 step 1.583 ms folded against 1.517 ms with the finish launches (C4: 2.917 against 2.721) -- an
-    // agent-scope release is an L2 write-back + invalidate on a chip whose eight XCD L2s are not coherent with each other, 256-1024 of
-    // them per pass.  Second form (no fence: sc1 stores / loads of exactly the values the last workgroup reads, nsos_last_block):
-    // 1.586 against 1.581 ms, C4 2.889 against 2.866 -- no slower any more and no faster either: the appearance loss's finish
-    // launches run on the side stream under the geometric loss, and ONE workgroup summing 8 k row sums through memory takes what the
-    // two 1024-thread finish blocks took.  NSOS_LOSS_FOLD_FINISH=1 selects the folded form (same bits: tests/test_gpu_losses.py).
-    const bool fold = phases == 7 && loss != nullptr && nsos_env_flag("NSOS_LOSS_FOLD_FINISH");
-    A.tickets = fold ? reinterpret_cast<unsigned*>(A.scal + 8) : nullptr;
-    A.nb = nb;
-    A.cnt = (double)B * N * N;
-    A.loss = loss;
-    A.flags = flags ? flags : A.scal;
-    A.geo = GEO ? 1 : 0;
     if (phases & 1) {
         hipLaunchKernelGGL((pair_rows_kernel<GEO, C, 1, NARROW>), grid, dim3(tb), lds_rows12, st, A);
-        if (GEO && A.Bg > 0 && A.Bg < B) {
-            if (fold) hipLaunchKernelGGL(pair_rowsum_copy_finish_kernel, dim3((N + 255) / 256, grid.y, 2), dim3(256), 0, st, A, (int)grid.x);
-            else hipLaunchKernelGGL(pair_rowsum_copy_kernel, dim3((N + 255) / 256, grid.y, 2), dim3(256), 0, st, A, (int)grid.x);
-        }
-        if (fold) {}
-        else if (phases & 2) hipLaunchKernelGGL(pass1_finish_kernel, dim3(2), dim3(1024), 0, st, A, nb);
+        if (GEO && A.Bg > 0 && A.Bg < B)
+            hipLaunchKernelGGL(pair_rowsum_copy_kernel, dim3((N + 255) / 256, grid.y, 2), dim3(256), 0, st, A, (int)grid.x);
+        if (phases & 2) hipLaunchKernelGGL(pass1_finish_kernel, dim3(2), dim3(1024), 0, st, A, nb);
         else hipLaunchKernelGGL(pair_finish_kernel, dim3(2), dim3(64), 0, st, A.partial, nb, A.scal, 0);
     } else if (phases & 2) hipLaunchKernelGGL(rowmean_residual_kernel, dim3(2), dim3(256), 0, st, A);
     if (phases & 4) {
@@ -1147,8 +1004,7 @@ int32_t run_pair_passes_shape(const PairArgs& A_in, bool want_grad, float* loss,
             if (fuse) hipLaunchKernelGGL((pair_rows_kernel<GEO, C, 3, NARROW, true>), grid, dim3(tb), lds_rows3, st, A);
         }
         if (!fuse) hipLaunchKernelGGL((pair_rows_kernel<GEO, C, 3, NARROW>), grid, dim3(tb), lds_rows3, st, A);
-        if (fold) {}
-        else if (loss) hipLaunchKernelGGL(pass3_finish_kernel, dim3(1), dim3(64), 0, st, A.partial, nb, A.scal, (double)B * N * N, A.prm, loss, GEO ? 1 : 0, flags ? flags : A.scal);
+        if (loss) hipLaunchKernelGGL(pass3_finish_kernel, dim3(1), dim3(64), 0, st, A.partial, nb, A.scal, (double)B * N * N, A.prm, loss, GEO ? 1 : 0, flags ? flags : A.scal);
         else hipLaunchKernelGGL(pair_finish_kernel, dim3(2), dim3(64), 0, st, A.partial, nb, A.scal, 4);
         if constexpr (kCanFuse) {
             if (fuse) hipLaunchKernelGGL((pair_cols_fold_kernel<C>), dim3((N + 63) / 64, grid.y, 2), dim3(256), 0, st, A, (int)grid.x);
@@ -1168,17 +1024,25 @@ int32_t run_pair_passes(const PairArgs& A, bool want_grad, float* loss, hipStrea
     return run_pair_passes_shape<GEO, C, false>(A, want_grad, loss, st, phases, flags);
 }
 
+// What every geometric evaluation starts with: the depth filter's maximum, then the back-projected points and the normalised codes
+// of the WHOLE batch
+template <int C>
+void geo_prepare(float* depth, const GeoInputs& in, int B, int N, float max_depth, int write_back, const Ws& w, hipStream_t st) {
+    const long long tot = (long long)B * N, tot_geo = (long long)in.Bg * N;      // depth: one map per GEOMETRY patch
+    const int rb = (int)((tot_geo + 255) / 256 < 256 ? (tot_geo + 255) / 256 : 256);
+    hipLaunchKernelGGL(depth_max_kernel, dim3(rb), dim3(256), 0, st, depth, tot_geo, max_depth, w.partial, w.scal);
+    hipLaunchKernelGGL((geo_prep_kernel<C>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, depth, in, B, N,
+                       max_depth, write_back, w.scal, w.pts, w.cn, w.dinv, w.partial, rb);
+}
+
 template <int C>
 int32_t geo_impl(float* depth, const GeoInputs in, const long long* neg, int B, int N,
                  CorrParams prm, float max_depth, int write_back, float* loss, void* workspace, hipStream_t st) {
     const bool want_grad = in.grad[0] != nullptr || in.grad[1] != nullptr;
     Ws w;
     ws_layout(&w, workspace, B, N, 0, false);
-    const long long tot = (long long)B * N, tot_geo = (long long)in.Bg * N;      // depth: one map per GEOMETRY patch
-    const int rb = (int)((tot_geo + 255) / 256 < 256 ? (tot_geo + 255) / 256 : 256);
-    hipLaunchKernelGGL(depth_max_kernel, dim3(rb), dim3(256), 0, st, depth, tot_geo, max_depth, w.partial, w.scal);
-    hipLaunchKernelGGL((geo_prep_kernel<C>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, depth, in, B, N,
-                       max_depth, write_back, w.scal, w.pts, w.cn, w.dinv, w.partial, rb);
+    const long long tot = (long long)B * N;
+    geo_prepare<C>(depth, in, B, N, max_depth, write_back, w, st);
     PairArgs A = {B, N, C, neg, w.pts, w.cn, nullptr, nullptr, w.rowsum, w.partial, w.scal, w.grow, w.gcol, max_depth, prm, nullptr, 0, w.gcolp, in.Bg};
     const int32_t rc = run_pair_passes<true, C>(A, want_grad, loss, st);
     if (rc != NSOS_OK) return rc;
@@ -1256,13 +1120,7 @@ int32_t geo_rows_impl(int phase, float* depth, const GeoInputs in, const long lo
     double* means = xmeans ? xmeans : w.scal;       // [0..5]; the depth maximum and the NaN flag ([6], [7]) stay in the workspace
     float* sums = xsums ? xsums : w.gsum;
     PairArgs A = {B, N, C, neg, w.pts, w.cn, nullptr, nullptr, w.rowsum, w.partial, means, w.grow, w.gcol, max_depth, prm, rows, n_rows, w.gcolp, in.Bg};
-    if (phase == 0 || phase == 3) {
-        const long long tot_geo = (long long)in.Bg * N;                            // depth: one map per GEOMETRY patch
-        const int rb = (int)((tot_geo + 255) / 256 < 256 ? (tot_geo + 255) / 256 : 256);
-        hipLaunchKernelGGL(depth_max_kernel, dim3(rb), dim3(256), 0, st, depth, tot_geo, max_depth, w.partial, w.scal);
-        hipLaunchKernelGGL((geo_prep_kernel<C>), dim3(gb), dim3(256), 0, st, depth, in, B, N, max_depth, write_back,
-                           w.scal, w.pts, w.cn, w.dinv, w.partial, rb);
-    }
+    if (phase == 0 || phase == 3) geo_prepare<C>(depth, in, B, N, max_depth, write_back, w, st);
     if (phase == 3) {   // single process: nothing to reduce between the phases -- every launch of the loss from one call
         if (n_rows == 0) {
             hipError_t e = hipMemsetAsync(means, 0, 6 * sizeof(double), st);
@@ -1308,7 +1166,7 @@ int32_t app_impl(const float* feats, const float* code, const long long* neg, co
     Ws w;
     ws_layout(&w, workspace, B, N, Cf, true);
     hipLaunchKernelGGL((app_sample_kernel<C>), dim3(N, B, 2), dim3(128), 0, st, feats, code, neg, rnd1, rnd2, B, Cf, Hf, Wf, Hc, Wc, S,
-                       w.fn, w.cn, w.cn2, w.dinv, w.dinv2, channel_last, nullptr, w.scal);
+                       w.fn, w.cn, w.cn2, w.dinv, w.dinv2, channel_last, nullptr);
     hipLaunchKernelGGL(app_fd_kernel, dim3(N, B, 2), dim3(1024), 0, st, w.fn, B, N, Cf, w.fdmat, nullptr);   // 16 waves x 2 column quads each: a short dependent chain
     PairArgs A = {B, N, C, neg, nullptr, w.cn, w.cn2, w.fdmat, w.rowsum, w.partial, w.scal, w.grow, w.gcol, 0.0f, prm, nullptr, 0, nullptr, 0};
     const int32_t rc = run_pair_passes<false, C>(A, grad_code != nullptr, loss, st);
@@ -1347,7 +1205,7 @@ int32_t app_rows_impl(int phase, const float* feats, const float* code, const lo
         if (e != hipSuccess) return (int32_t)e;
         if (n_rows == 0) return nsos_launch_status();
         hipLaunchKernelGGL((app_sample_kernel<C>), dim3(N, n_rows, 2), dim3(128), 0, st, feats, code, neg, rnd1, rnd2, B, Cf, Hf, Wf, Hc, Wc, S,
-                           w.fn, w.cn, w.cn2, w.dinv, w.dinv2, channel_last, rows, w.scal);
+                           w.fn, w.cn, w.cn2, w.dinv, w.dinv2, channel_last, rows);
         hipLaunchKernelGGL(app_fd_kernel, dim3(N, n_rows, 2), dim3(1024), 0, st, w.fn, B, N, Cf, w.fdmat, rows);
         return run_pair_passes<false, C>(A, true, nullptr, st, 3);
     }
@@ -1376,6 +1234,17 @@ int32_t app_rows_impl(int phase, const float* feats, const float* code, const lo
     return nsos_launch_status();
 }
 
+// f(std::integral_constant<int, C>{}) for the code width of the call (the entries admit 1..kMaxC before they get here)
+template <class F>
+int32_t with_code_dim(int code_dim, F&& f) {
+    switch (code_dim) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ C ABI
@@ -1383,31 +1252,6 @@ extern "C" size_t nsos_corr_workspace_bytes(int32_t kind, int32_t batch, int32_t
     if (batch <= 0 || n_points <= 0 || (kind != 0 && kind != 1)) return 0;
     const int cf = kind == 0 ? (feat_dim < 2 * kMaxC ? 2 * kMaxC : feat_dim) : 0;
     return ws_layout(nullptr, nullptr, batch, n_points, cf, kind == 0);
-}
-
-extern "C" int32_t nsos_geo_correlation_loss(float* depth, const float* code, const float* ray_o, const float* ray_d,
-                                             const int64_t* neg_indx, int32_t batch, int32_t code_dim, int32_t height,
-                                             int32_t width, float self_shift, float self_weight, float neg_shift,
-                                             float neg_weight, float max_depth, int32_t filter_in_place, float* loss,
-                                             float* grad_code, void* workspace, size_t workspace_bytes, void* stream) {
-    if (batch == 0) return NSOS_OK;
-    NSOS_REQUIRE(depth && code && ray_o && ray_d && neg_indx && loss && workspace, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(batch > 0 && height > 0 && width > 0, NSOS_ERR_BAD_SHAPE);
-    NSOS_REQUIRE(code_dim >= 1 && code_dim <= kMaxC, NSOS_ERR_UNSUPPORTED);
-    const long long N = (long long)height * width;
-    NSOS_REQUIRE(N <= 4096, NSOS_ERR_UNSUPPORTED);   // one patch's points + codes + row means stay resident in LDS
-    NSOS_REQUIRE(((uintptr_t)workspace & 15) == 0, NSOS_ERR_MISALIGNED);
-    NSOS_REQUIRE(workspace_bytes >= nsos_corr_workspace_bytes(1, batch, (int32_t)N, 0), NSOS_ERR_BUFFER_TOO_SMALL);
-    const CorrParams prm = {self_shift, self_weight, neg_shift, neg_weight};
-    const long long* neg = reinterpret_cast<const long long*>(neg_indx);
-    const hipStream_t st = (hipStream_t)stream;
-    const GeoInputs in = {{code, nullptr}, {grad_code, nullptr}, ray_o, ray_d, batch, 1, 0};
-    switch (code_dim) {
-        case 1: return geo_impl<1>(depth, in, neg, batch, (int)N, prm, max_depth, filter_in_place, loss, workspace, st);
-        case 2: return geo_impl<2>(depth, in, neg, batch, (int)N, prm, max_depth, filter_in_place, loss, workspace, st);
-        case 3: return geo_impl<3>(depth, in, neg, batch, (int)N, prm, max_depth, filter_in_place, loss, workspace, st);
-        default: return geo_impl<4>(depth, in, neg, batch, (int)N, prm, max_depth, filter_in_place, loss, workspace, st);
-    }
 }
 
 extern "C" int32_t nsos_corr_workspace_slots(int32_t batch, int32_t n_points, int64_t* scal_offset_bytes,
@@ -1425,10 +1269,11 @@ extern "C" int64_t nsos_corr_exchange_floats(int32_t batch, int32_t n_points) {
     return batch > 0 && n_points > 0 ? (int64_t)batch * n_points * kMaxC + kSumTail : 0;
 }
 
-static int32_t geo_rows_entry(int32_t phase, float* depth, const GeoInputs in, const int64_t* neg_indx, const int32_t* rows, int32_t n_rows,
-                              int32_t code_dim, int32_t height, int32_t width, float self_shift, float self_weight, float neg_shift,
-                              float neg_weight, float max_depth, int32_t filter_in_place, float* loss, void* workspace,
-                              size_t workspace_bytes, double* xmeans, float* xsums, void* stream) {
+// The checks of the three geometric entries, in the order callers have come to know (tests/test_abi.py pins the code of every
+// refusal and which of two faults is reported).  The plain entry is phase 3 without a row list or exchange buffers.
+static int32_t geo_check(int32_t phase, const float* depth, const GeoInputs& in, const int64_t* neg_indx, const int32_t* rows, int32_t n_rows,
+                         int32_t code_dim, int32_t height, int32_t width, const float* loss, const void* workspace, size_t workspace_bytes,
+                         const double* xmeans, const float* xsums) {
     const int batch = in.Bg * in.n_codes;
     NSOS_REQUIRE(phase >= 0 && phase <= 3, NSOS_ERR_UNSUPPORTED);
     NSOS_REQUIRE((((uintptr_t)xmeans) & 7) == 0 && (((uintptr_t)xsums) & 3) == 0, NSOS_ERR_MISALIGNED);
@@ -1438,18 +1283,39 @@ static int32_t geo_rows_entry(int32_t phase, float* depth, const GeoInputs in, c
     NSOS_REQUIRE(batch > 0 && height > 0 && width > 0 && n_rows >= 0 && n_rows <= batch, NSOS_ERR_BAD_SHAPE);
     NSOS_REQUIRE(code_dim >= 1 && code_dim <= kMaxC, NSOS_ERR_UNSUPPORTED);
     const long long N = (long long)height * width;
-    NSOS_REQUIRE(N <= 4096, NSOS_ERR_UNSUPPORTED);
+    NSOS_REQUIRE(N <= 4096, NSOS_ERR_UNSUPPORTED);   // one patch's points + codes + row means stay resident in LDS
     NSOS_REQUIRE(((uintptr_t)workspace & 15) == 0, NSOS_ERR_MISALIGNED);
     NSOS_REQUIRE(workspace_bytes >= nsos_corr_workspace_bytes(1, batch, (int32_t)N, 0), NSOS_ERR_BUFFER_TOO_SMALL);
+    return NSOS_OK;
+}
+
+extern "C" int32_t nsos_geo_correlation_loss(float* depth, const float* code, const float* ray_o, const float* ray_d,
+                                             const int64_t* neg_indx, int32_t batch, int32_t code_dim, int32_t height,
+                                             int32_t width, float self_shift, float self_weight, float neg_shift,
+                                             float neg_weight, float max_depth, int32_t filter_in_place, float* loss,
+                                             float* grad_code, void* workspace, size_t workspace_bytes, void* stream) {
+    if (batch == 0) return NSOS_OK;
+    const GeoInputs in = {{code, nullptr}, {grad_code, nullptr}, ray_o, ray_d, batch, 1, 0};
+    const int32_t rc = geo_check(3, depth, in, neg_indx, nullptr, 0, code_dim, height, width, loss, workspace, workspace_bytes, nullptr, nullptr);
+    if (rc != NSOS_OK) return rc;
     const CorrParams prm = {self_shift, self_weight, neg_shift, neg_weight};
-    const long long* neg = reinterpret_cast<const long long*>(neg_indx);
-    const hipStream_t st = (hipStream_t)stream;
-    switch (code_dim) {
-        case 1: return geo_rows_impl<1>(phase, depth, in, neg, rows, n_rows, batch, (int)N, prm, max_depth, filter_in_place, loss, workspace, xmeans, xsums, st);
-        case 2: return geo_rows_impl<2>(phase, depth, in, neg, rows, n_rows, batch, (int)N, prm, max_depth, filter_in_place, loss, workspace, xmeans, xsums, st);
-        case 3: return geo_rows_impl<3>(phase, depth, in, neg, rows, n_rows, batch, (int)N, prm, max_depth, filter_in_place, loss, workspace, xmeans, xsums, st);
-        default: return geo_rows_impl<4>(phase, depth, in, neg, rows, n_rows, batch, (int)N, prm, max_depth, filter_in_place, loss, workspace, xmeans, xsums, st);
-    }
+    return with_code_dim(code_dim, [&](auto c) {
+        return geo_impl<decltype(c)::value>(depth, in, reinterpret_cast<const long long*>(neg_indx), batch, height * width, prm, max_depth,
+                                            filter_in_place, loss, workspace, (hipStream_t)stream);
+    });
+}
+
+static int32_t geo_rows_entry(int32_t phase, float* depth, const GeoInputs in, const int64_t* neg_indx, const int32_t* rows, int32_t n_rows,
+                              int32_t code_dim, int32_t height, int32_t width, float self_shift, float self_weight, float neg_shift,
+                              float neg_weight, float max_depth, int32_t filter_in_place, float* loss, void* workspace,
+                              size_t workspace_bytes, double* xmeans, float* xsums, void* stream) {
+    const int32_t rc = geo_check(phase, depth, in, neg_indx, rows, n_rows, code_dim, height, width, loss, workspace, workspace_bytes, xmeans, xsums);
+    if (rc != NSOS_OK) return rc;
+    const CorrParams prm = {self_shift, self_weight, neg_shift, neg_weight};
+    return with_code_dim(code_dim, [&](auto c) {
+        return geo_rows_impl<decltype(c)::value>(phase, depth, in, reinterpret_cast<const long long*>(neg_indx), rows, n_rows, in.Bg * in.n_codes,
+                                                 height * width, prm, max_depth, filter_in_place, loss, workspace, xmeans, xsums, (hipStream_t)stream);
+    });
 }
 
 extern "C" int32_t nsos_geo_correlation_loss_rows(int32_t phase, float* depth, const float* code, const float* ray_o,
@@ -1480,28 +1346,38 @@ extern "C" int32_t nsos_geo_correlation_loss_pair(int32_t phase, const float* de
                           neg_shift, neg_weight, max_depth, 0, loss, workspace, workspace_bytes, exchange_means, exchange_sums, stream);
 }
 
+// The checks of the three appearance entries, in their order (tests/test_abi.py, as for geo_check; here the exchange buffers' alignment
+// is looked at with the workspace's, after the pointers and the shapes).  The single-process entries are phase 2 -- the one that
+// writes the loss -- without a row list or exchange buffers.
+static int32_t app_check(int32_t phase, const float* feats, const float* code, const int64_t* neg_indx, const float* rand1, const float* rand2,
+                         const int32_t* rows, int32_t n_rows, int32_t batch, int32_t feat_dim, int32_t feat_h, int32_t feat_w, int32_t code_dim,
+                         int32_t code_h, int32_t code_w, int32_t feature_samples, const float* loss, const void* workspace,
+                         size_t workspace_bytes, const double* xmeans, const float* xsums) {
+    NSOS_REQUIRE(phase >= 0 && phase <= 2, NSOS_ERR_UNSUPPORTED);      // (one process: nsos_app_correlation_loss[_nhwc])
+    NSOS_REQUIRE(feats && code && neg_indx && rand1 && rand2 && workspace && (n_rows == 0 || rows) && (phase < 2 || loss), NSOS_ERR_NULL_POINTER);
+    NSOS_REQUIRE(batch > 0 && feat_dim > 0 && feat_h > 0 && feat_w > 0 && code_h > 0 && code_w > 0 && feature_samples > 0 && n_rows >= 0 &&
+                 n_rows <= batch, NSOS_ERR_BAD_SHAPE);
+    NSOS_REQUIRE(code_dim >= 1 && code_dim <= kMaxC, NSOS_ERR_UNSUPPORTED);
+    const int N = feature_samples * feature_samples;
+    NSOS_REQUIRE(N <= 1024, NSOS_ERR_UNSUPPORTED);
+    NSOS_REQUIRE(((uintptr_t)workspace & 15) == 0 && (((uintptr_t)xmeans) & 7) == 0 && (((uintptr_t)xsums) & 3) == 0, NSOS_ERR_MISALIGNED);
+    NSOS_REQUIRE(workspace_bytes >= nsos_corr_workspace_bytes(0, batch, N, feat_dim), NSOS_ERR_BUFFER_TOO_SMALL);
+    return NSOS_OK;
+}
+
 static int32_t app_entry(const float* feats, const float* code, const int64_t* neg_indx, const float* rand1, const float* rand2,
                          int32_t batch, int32_t feat_dim, int32_t feat_h, int32_t feat_w, int32_t code_dim, int32_t code_h, int32_t code_w,
                          int32_t feature_samples, float self_shift, float self_weight, float neg_shift, float neg_weight, float* loss,
                          float* grad_code, void* workspace, size_t workspace_bytes, void* stream, int channel_last) {
     if (batch == 0) return NSOS_OK;
-    NSOS_REQUIRE(feats && code && neg_indx && rand1 && rand2 && loss && workspace, NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(batch > 0 && feat_dim > 0 && feat_h > 0 && feat_w > 0 && code_h > 0 && code_w > 0 && feature_samples > 0,
-                 NSOS_ERR_BAD_SHAPE);
-    NSOS_REQUIRE(code_dim >= 1 && code_dim <= kMaxC, NSOS_ERR_UNSUPPORTED);
-    const int N = feature_samples * feature_samples;
-    NSOS_REQUIRE(N <= 1024, NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(((uintptr_t)workspace & 15) == 0, NSOS_ERR_MISALIGNED);
-    NSOS_REQUIRE(workspace_bytes >= nsos_corr_workspace_bytes(0, batch, N, feat_dim), NSOS_ERR_BUFFER_TOO_SMALL);
+    const int32_t rc = app_check(2, feats, code, neg_indx, rand1, rand2, nullptr, 0, batch, feat_dim, feat_h, feat_w, code_dim, code_h, code_w,
+                                 feature_samples, loss, workspace, workspace_bytes, nullptr, nullptr);
+    if (rc != NSOS_OK) return rc;
     const CorrParams prm = {self_shift, self_weight, neg_shift, neg_weight};
-    const long long* neg = reinterpret_cast<const long long*>(neg_indx);
-    const hipStream_t st = (hipStream_t)stream;
-    switch (code_dim) {
-        case 1: return app_impl<1>(feats, code, neg, rand1, rand2, batch, feat_dim, feat_h, feat_w, code_h, code_w, feature_samples, prm, loss, grad_code, workspace, st, channel_last);
-        case 2: return app_impl<2>(feats, code, neg, rand1, rand2, batch, feat_dim, feat_h, feat_w, code_h, code_w, feature_samples, prm, loss, grad_code, workspace, st, channel_last);
-        case 3: return app_impl<3>(feats, code, neg, rand1, rand2, batch, feat_dim, feat_h, feat_w, code_h, code_w, feature_samples, prm, loss, grad_code, workspace, st, channel_last);
-        default: return app_impl<4>(feats, code, neg, rand1, rand2, batch, feat_dim, feat_h, feat_w, code_h, code_w, feature_samples, prm, loss, grad_code, workspace, st, channel_last);
-    }
+    return with_code_dim(code_dim, [&](auto c) {
+        return app_impl<decltype(c)::value>(feats, code, reinterpret_cast<const long long*>(neg_indx), rand1, rand2, batch, feat_dim, feat_h, feat_w,
+                                            code_h, code_w, feature_samples, prm, loss, grad_code, workspace, (hipStream_t)stream, channel_last);
+    });
 }
 
 extern "C" int32_t nsos_app_correlation_loss(const float* feats, const float* code, const int64_t* neg_indx,
@@ -1532,26 +1408,13 @@ extern "C" int32_t nsos_app_correlation_loss_rows(int32_t phase, const float* fe
                                                   float* grad_code, void* workspace, size_t workspace_bytes, double* exchange_means,
                                                   float* exchange_sums, void* stream) {
     if (batch == 0) return NSOS_OK;
-    NSOS_REQUIRE(phase >= 0 && phase <= 2, NSOS_ERR_UNSUPPORTED);      // (one process: nsos_app_correlation_loss[_nhwc])
-    NSOS_REQUIRE(feats && code && neg_indx && rand1 && rand2 && workspace && (n_rows == 0 || rows) && (phase < 2 || loss), NSOS_ERR_NULL_POINTER);
-    NSOS_REQUIRE(batch > 0 && feat_dim > 0 && feat_h > 0 && feat_w > 0 && code_h > 0 && code_w > 0 && feature_samples > 0 && n_rows >= 0 &&
-                 n_rows <= batch, NSOS_ERR_BAD_SHAPE);
-    NSOS_REQUIRE(code_dim >= 1 && code_dim <= kMaxC, NSOS_ERR_UNSUPPORTED);
-    const int N = feature_samples * feature_samples;
-    NSOS_REQUIRE(N <= 1024, NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(((uintptr_t)workspace & 15) == 0 && (((uintptr_t)exchange_means) & 7) == 0 && (((uintptr_t)exchange_sums) & 3) == 0, NSOS_ERR_MISALIGNED);
-    NSOS_REQUIRE(workspace_bytes >= nsos_corr_workspace_bytes(0, batch, N, feat_dim), NSOS_ERR_BUFFER_TOO_SMALL);
+    const int32_t rc = app_check(phase, feats, code, neg_indx, rand1, rand2, rows, n_rows, batch, feat_dim, feat_h, feat_w, code_dim, code_h, code_w,
+                                 feature_samples, loss, workspace, workspace_bytes, exchange_means, exchange_sums);
+    if (rc != NSOS_OK) return rc;
     const CorrParams prm = {self_shift, self_weight, neg_shift, neg_weight};
-    const long long* neg = reinterpret_cast<const long long*>(neg_indx);
-    const hipStream_t st = (hipStream_t)stream;
-#define NSOS_APP_ROWS(CC)                                                                                                                    \
-    return app_rows_impl<CC>(phase, feats, code, neg, rand1, rand2, rows, n_rows, batch, feat_dim, feat_h, feat_w, code_h, code_w, feature_samples, \
-                             prm, loss, grad_code, workspace, exchange_means, exchange_sums, st, channel_last != 0)
-    switch (code_dim) {
-        case 1: NSOS_APP_ROWS(1);
-        case 2: NSOS_APP_ROWS(2);
-        case 3: NSOS_APP_ROWS(3);
-        default: NSOS_APP_ROWS(4);
-    }
-#undef NSOS_APP_ROWS
+    return with_code_dim(code_dim, [&](auto c) {
+        return app_rows_impl<decltype(c)::value>(phase, feats, code, reinterpret_cast<const long long*>(neg_indx), rand1, rand2, rows, n_rows, batch,
+                                                 feat_dim, feat_h, feat_w, code_h, code_w, feature_samples, prm, loss, grad_code, workspace,
+                                                 exchange_means, exchange_sums, (hipStream_t)stream, channel_last != 0);
+    });
 }

@@ -9,13 +9,16 @@ No CPU path: inputs must be GPU tensors and the HIP library must be present.
 """
 from __future__ import annotations
 
+import ctypes as C_
 from typing import Optional, Sequence
 
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib
 from .ops import _dev, _p, _stream
+from .sharding import collective, device_index, multi_process
 
 
 def _params_of(values: Sequence, defaults):
@@ -32,9 +35,6 @@ def _run_phases(run, ws: torch.Tensor, batch: int, n_points: int, group) -> None
     """A row-partitioned geometric evaluation on its own: phase 3 (everything in one call) without a process group; with one,
     phases 0..2 and the two sum-all-reduces of its workspace slots in between.  Every rank issues both reductions (a rank that
     owns no patch contributes zeros): the sequence of collectives does not depend on the data."""
-    import ctypes as C_
-    import torch.distributed as dist
-    from .sharding import collective, multi_process
     if not multi_process(group):
         run(3)
         return
@@ -47,6 +47,12 @@ def _run_phases(run, ws: torch.Tensor, batch: int, n_points: int, group) -> None
     run(1)
     collective("loss_sums_all_reduce", lambda async_op: dist.all_reduce(sums, group=group, async_op=async_op), group)
     run(2)
+
+
+def _workspace(kind: int, batch: int, n_points: int, feat_dim: int, dev) -> torch.Tensor:
+    """The fp64 tensor one evaluation works in: `nsos_corr_workspace_bytes` (kind 0 = appearance, 1 = geometric), whole 16 bytes."""
+    nbytes = _lib.lib().nsos_corr_workspace_bytes(kind, batch, n_points, feat_dim)
+    return torch.empty((nbytes + 15) // 16 * 2, device=dev, dtype=torch.float64)
 
 
 def _is_channel_last_view(t: torch.Tensor) -> bool:
@@ -138,50 +144,48 @@ class CorrelationLoss(nn.Module):
         forward / value_and_grad calls that are not handed `coords` themselves."""
         self._queued = list(coords)
 
-    def _launcher(self, orig_feats: torch.Tensor, code_shape, sim_matrix: Optional[torch.Tensor], weight: float = 1.0,
-                  neg: Optional[torch.Tensor] = None, coords: Optional[torch.Tensor] = None, loss_out: Optional[torch.Tensor] = None):
-        if coords is None and getattr(self, "_queued", None):
-            coords = self._queued.pop(0)
-        """Draws the sample coordinates and the negatives (the reference's order: rand1, rand2, negatives) and returns
-        launch(code, want_grad) -> (weight * loss, weight * d loss / d code or None).  `weight` rides on the kernel's own
-        self / negative weights (no extra launch); `neg`: negatives computed by the caller (one argmin per step, not per call)."""
+    def _inputs(self, orig_feats: torch.Tensor, code_shape, sim_matrix: Optional[torch.Tensor], weight: float, neg: Optional[torch.Tensor],
+                coords: Optional[torch.Tensor]):
+        """What _launcher and rows_phased start from: (feats, rand1, rand2, neg, prm).  The sample coordinates are the caller's `coords`
+        (draw_coords) or two draws here, then the negatives: the reference's order (rand1, rand2, negatives).  `neg`: negatives computed
+        by the caller (one argmin per step, not per call); `weight` rides on the kernel's own self / negative weights (no extra launch)."""
         feats = _dev(orig_feats.detach(), "orig_feats")
-        B, Cf, Hf, Wf = feats.shape
-        Bc, C, Hc, Wc = code_shape
-        if Bc != B:
-            raise ValueError(f"orig_feats has {B} patches, orig_code {Bc}")
-        S = self.feature_samples
-        dev = feats.device
-        if coords is not None:                                                                           # drawn by the caller (draw_coords)
+        B, S, dev = feats.shape[0], self.feature_samples, feats.device
+        if code_shape[0] != B:
+            raise ValueError(f"orig_feats has {B} patches, orig_code {code_shape[0]}")
+        if coords is not None:
             rand1, rand2 = _dev(coords[0], "coords"), _dev(coords[1], "coords")
         else:
             rand1 = torch.rand([B, S, S, 2], device=dev, generator=self.generator)                       # :343 (the kernel applies *2-1)
             rand2 = torch.rand([B, S, S, 2], device=dev, generator=self.generator)                       # :344
         if neg is None:
             neg = self._neg_index(sim_matrix, B, dev)
-        lib = _lib.lib()
         w = float(weight)
-        prm = (self.self_shift, self.self_weight * w, self.neg_shift, self.neg_weight * w)
+        return feats, rand1, rand2, neg, (self.self_shift, self.self_weight * w, self.neg_shift, self.neg_weight * w)
+
+    def _launcher(self, orig_feats: torch.Tensor, code_shape, sim_matrix: Optional[torch.Tensor], weight: float = 1.0,
+                  neg: Optional[torch.Tensor] = None, coords: Optional[torch.Tensor] = None, loss_out: Optional[torch.Tensor] = None):
+        """Draws the sample coordinates and the negatives (_inputs; queued coordinates are consumed here only) and returns
+        launch(code, want_grad) -> (weight * loss, weight * d loss / d code or None)."""
+        if coords is None and getattr(self, "_queued", None):
+            coords = self._queued.pop(0)
+        feats, rand1, rand2, neg, prm = self._inputs(orig_feats, code_shape, sim_matrix, weight, neg, coords)
+        B, Cf, Hf, Wf = feats.shape
+        _, C, Hc, Wc = code_shape
+        S, dev, lib = self.feature_samples, feats.device, _lib.lib()
 
         def launch(code, want_grad):
             code = code.detach()
-            nbytes = lib.nsos_corr_workspace_bytes(0, B, S * S, Cf)
-            ws = torch.empty((nbytes + 15) // 16 * 2, device=dev, dtype=torch.float64)
+            # the renderer's `semantics` [B,P,P,C] seen through .permute(0,3,1,2) is read (and differentiated) in place
+            nhwc = _is_channel_last_view(code)
+            code = _dev(code.permute(0, 2, 3, 1) if nhwc else code, "orig_code")
+            name = "nsos_app_correlation_loss_nhwc" if nhwc else "nsos_app_correlation_loss"
+            ws = _workspace(0, B, S * S, Cf, dev)
             loss = loss_out if loss_out is not None else torch.empty((), device=dev, dtype=torch.float32)   # (loss_out: a slot of the step's loss buffer)
-            if _is_channel_last_view(code):
-                # the renderer's `semantics` [B,P,P,C] seen through .permute(0,3,1,2): read (and differentiated) in place
-                nhwc = _dev(code.permute(0, 2, 3, 1), "orig_code")
-                g = torch.empty_like(nhwc) if want_grad else None
-                _lib.check(lib.nsos_app_correlation_loss_nhwc(_p(feats), _p(nhwc), neg.data_ptr(), _p(rand1), _p(rand2), B, Cf, Hf, Wf,
-                                                              C, Hc, Wc, S, *prm, _p(loss), _p(g), ws.data_ptr(), ws.numel() * 8,
-                                                              _stream()), "nsos_app_correlation_loss_nhwc")
-                return loss, (g.permute(0, 3, 1, 2) if want_grad else None)
-            code = _dev(code, "orig_code")
             grad = torch.empty_like(code) if want_grad else None
-            _lib.check(lib.nsos_app_correlation_loss(_p(feats), _p(code), neg.data_ptr(), _p(rand1), _p(rand2), B, Cf, Hf, Wf, C,
-                                                     Hc, Wc, S, *prm, _p(loss), _p(grad), ws.data_ptr(), ws.numel() * 8,
-                                                     _stream()), "nsos_app_correlation_loss")
-            return loss, grad
+            _lib.check(getattr(lib, name)(_p(feats), _p(code), neg.data_ptr(), _p(rand1), _p(rand2), B, Cf, Hf, Wf, C, Hc, Wc, S, *prm,
+                                          _p(loss), _p(grad), ws.data_ptr(), ws.numel() * 8, _stream()), name)
+            return loss, (grad.permute(0, 3, 1, 2) if nhwc and want_grad else grad)
 
         return launch
 
@@ -194,31 +198,16 @@ class CorrelationLoss(nn.Module):
         after phase 2 `loss` is the batch-wide value on every rank and `grad` [B,C,P,P] holds weight * d loss / d code for the
         patches in `rows` (zeros elsewhere).  exchange = (means [8] fp64, sums [exchange_floats(B, S S)] fp32): slices of the two
         buffers the step reduces once per phase for all of its evaluations."""
-        feats = _dev(orig_feats.detach(), "orig_feats")
+        feats, rand1, rand2, neg, prm = self._inputs(orig_feats, orig_code.shape, sim_matrix, weight, neg, coords)
         B, Cf, Hf, Wf = feats.shape
-        Bc, C, Hc, Wc = orig_code.shape
-        if Bc != B:
-            raise ValueError(f"orig_feats has {B} patches, orig_code {Bc}")
-        S = self.feature_samples
-        dev = feats.device
-        if coords is not None:
-            rand1, rand2 = _dev(coords[0], "coords"), _dev(coords[1], "coords")
-        else:
-            rand1 = torch.rand([B, S, S, 2], device=dev, generator=self.generator)                       # :343
-            rand2 = torch.rand([B, S, S, 2], device=dev, generator=self.generator)                       # :344
-        if neg is None:
-            neg = self._neg_index(sim_matrix, B, dev)
-        lib = _lib.lib()
-        w = float(weight)
-        prm = (self.self_shift, self.self_weight * w, self.neg_shift, self.neg_weight * w)
+        _, C, Hc, Wc = orig_code.shape
+        S, dev, lib = self.feature_samples, feats.device, _lib.lib()
         code = orig_code.detach()
         nhwc = _is_channel_last_view(code)
-        code = _dev(code.permute(0, 2, 3, 1), "orig_code") if nhwc else _dev(code, "orig_code")
+        code = _dev(code.permute(0, 2, 3, 1) if nhwc else code, "orig_code")
         grad = torch.empty_like(code)
         loss = loss_out if loss_out is not None else torch.empty((), device=dev, dtype=torch.float32)
-        nbytes = lib.nsos_corr_workspace_bytes(0, B, S * S, Cf)
-        ws = torch.empty((nbytes + 15) // 16 * 2, device=dev, dtype=torch.float64)
-        from .sharding import device_index
+        ws = _workspace(0, B, S * S, Cf, dev)
         rows_t = device_index(rows, torch.int32, dev)
         xm, xs = exchange
 
@@ -283,8 +272,7 @@ class GeoCorrelationLoss(CorrelationLoss):
 
         def launch(code, want_grad):
             code = _dev(code.detach(), "orig_code")
-            nbytes = lib.nsos_corr_workspace_bytes(1, B, H * W, 0)
-            ws = torch.empty((nbytes + 15) // 16 * 2, device=dev, dtype=torch.float64)
+            ws = _workspace(1, B, H * W, 0, dev)
             loss = torch.empty((), device=dev, dtype=torch.float32)
             grad = torch.empty_like(code) if want_grad else None
             if rows is None:
@@ -292,7 +280,6 @@ class GeoCorrelationLoss(CorrelationLoss):
                                                          float(self.max_depth), 1, _p(loss), _p(grad), ws.data_ptr(),
                                                          ws.numel() * 8, _stream()), "nsos_geo_correlation_loss")
                 return loss, grad
-            from .sharding import device_index
             rows_t = device_index(rows, torch.int32, dev)     # uploaded once (a fresh torch.tensor(..., device=) synchronises)
 
             def run(phase):
@@ -338,10 +325,8 @@ class GeoCorrelationLoss(CorrelationLoss):
         def launch(c0, c1, want_grad, exchange=None):
             """exchange = (means, sums): slices of the step's two reduction buffers -- returns the phase runner instead of running
             (the caller interleaves the phases of several evaluations with ONE all-reduce per phase: sharding._losses_direct)."""
-            from .sharding import device_index
             c0, c1 = _dev(c0.detach(), "code0"), _dev(c1.detach(), "code1")
-            nbytes = lib.nsos_corr_workspace_bytes(1, 2 * B, H * W, 0)
-            ws = torch.empty((nbytes + 15) // 16 * 2, device=dev, dtype=torch.float64)
+            ws = _workspace(1, 2 * B, H * W, 0, dev)
             loss = loss_out if loss_out is not None else torch.empty((), device=dev, dtype=torch.float32)
             g0 = torch.empty_like(c0) if want_grad else None
             g1 = torch.empty_like(c1) if want_grad else None

@@ -603,3 +603,136 @@ def test_mlp_entry_points_refuse_what_they_refused_before():
             assert _call_mlp_entry(lib, name, change, buf) == want, (name, case)
             n += 1
     assert n > 700
+
+
+# ---- refusals of the six correlation-loss entry points ----------------------------------------------------------------
+# Argument names in ABI order.  A name that _LOSS_BASE does not list is a pointer: non-NULL and 16-byte aligned by default.
+_F4 = ("self_shift", "self_weight", "neg_shift", "neg_weight")
+_GEO_TAIL = ("workspace", "workspace_bytes", "exchange_means", "exchange_sums", "stream")
+_APP_DIMS = ("feat_dim", "feat_h", "feat_w", "code_dim", "code_h", "code_w", "feature_samples")
+_APP = (("feats", "code", "neg", "rand1", "rand2", "batch") + _APP_DIMS + _F4 + ("loss", "grad", "workspace", "workspace_bytes", "stream"))
+_LOSS_ENTRIES = {
+    "nsos_geo_correlation_loss": ("depth", "code", "ray_o", "ray_d", "neg", "batch", "code_dim", "height", "width") + _F4
+                                 + ("max_depth", "filter_in_place", "loss", "grad", "workspace", "workspace_bytes", "stream"),
+    "nsos_geo_correlation_loss_rows": ("phase", "depth", "code", "ray_o", "ray_d", "neg", "rows", "n_rows", "batch", "code_dim", "height",
+                                       "width") + _F4 + ("max_depth", "filter_in_place", "loss", "grad") + _GEO_TAIL,
+    "nsos_geo_correlation_loss_pair": ("phase", "depth", "code", "code1", "ray_o", "ray_d", "neg", "rows", "n_rows", "batch", "channel_last",
+                                       "code_dim", "height", "width") + _F4 + ("max_depth", "loss", "grad", "grad1") + _GEO_TAIL,
+    "nsos_app_correlation_loss": _APP,
+    "nsos_app_correlation_loss_nhwc": _APP,
+    "nsos_app_correlation_loss_rows": ("phase", "feats", "code", "neg", "rand1", "rand2", "rows", "n_rows", "batch", "channel_last") + _APP_DIMS
+                                      + _F4 + ("loss", "grad") + _GEO_TAIL,
+}
+_LOSS_BASE = dict(batch=2, n_rows=2, channel_last=0, code_dim=2, height=8, width=8, feat_dim=7, feat_h=5, feat_w=3, code_h=13, code_w=20,
+                  feature_samples=11, self_shift=0.5, self_weight=1.0, neg_shift=3.0, neg_weight=1.0, max_depth=15.0, filter_in_place=1,
+                  exchange_means=None, exchange_sums=None, stream=None)
+_LAST_PHASE = {"nsos_geo_correlation_loss_rows": 3, "nsos_geo_correlation_loss_pair": 3, "nsos_app_correlation_loss_rows": 2}
+
+
+class _Off(int):
+    """a pointer argument this many bytes behind the aligned buffer"""
+
+
+_NULL_, _SHAPE_, _UNSUP_, _SMALL_, _MISAL_ = -1, -2, -3, -4, -5
+# The base call is right in everything but `workspace_bytes`, which is ONE short of nsos_corr_workspace_bytes(...): the last check of
+# every entry, so the base call returns _SMALL_ without a launch and every earlier fault shows through it.  Each row: what is changed
+# in the base call -> the code, a literal read off the entry points before their checks were shared (and confirmed on that library).
+_GEO_COMMON = [
+    (dict(grad=None), _SMALL_),                                            # the gradient is optional
+    (dict(height=0), _SHAPE_), (dict(width=0), _SHAPE_),
+    (dict(code_dim=0), _UNSUP_), (dict(code_dim=5), _UNSUP_),
+    (dict(height=65, width=64), _UNSUP_),                                  # N = 4160 > 4096
+    (dict(workspace=_Off(8)), _MISAL_),
+    (dict(), _SMALL_),                                                     # workspace_bytes one short
+    (dict(code_dim=5, workspace_bytes=0), _UNSUP_),                        # two faults: the code width is checked before the size
+    (dict(height=65, width=64, workspace=_Off(8)), _UNSUP_),               # ... N before the workspace's alignment
+    (dict(depth=None, height=0), _NULL_),                                  # ... pointers before shapes
+]
+_ROWS_COMMON = [                                                           # the four entries with phases, rows and exchange buffers
+    (dict(phase=-1), _UNSUP_),
+    (dict(rows=None), _NULL_), (dict(rows=None, n_rows=0), _SMALL_),       # no rows: no list needed
+    (dict(phase=0, loss=None), _SMALL_), (dict(phase=1, loss=None), _SMALL_), (dict(phase=2, loss=None), _NULL_),
+    (dict(n_rows=-1), _SHAPE_),
+    (dict(exchange_means=_Off(0), exchange_sums=_Off(0)), _SMALL_),
+    (dict(exchange_means=_Off(4)), _MISAL_), (dict(exchange_sums=_Off(2)), _MISAL_),
+]
+_GEO_ROWS_COMMON = _GEO_COMMON + _ROWS_COMMON + [
+    (dict(phase=4), _UNSUP_), (dict(phase=3, loss=None), _NULL_),
+    (dict(phase=4, depth=None), _UNSUP_),                                  # two faults: the phase comes first,
+    (dict(exchange_means=_Off(4), depth=None), _MISAL_),                   # then the exchange buffers' alignment, then the pointers
+    (dict(exchange_sums=_Off(2), rows=None), _MISAL_),
+    (dict(exchange_means=_Off(4), code_dim=5), _MISAL_),
+    (dict(loss=None, height=0), _NULL_),
+]
+_APP_COMMON = [
+    (dict(grad=None), _SMALL_),
+    (dict(feat_dim=0), _SHAPE_), (dict(feat_h=0), _SHAPE_), (dict(feat_w=0), _SHAPE_), (dict(code_h=0), _SHAPE_), (dict(code_w=0), _SHAPE_),
+    (dict(feature_samples=0), _SHAPE_), (dict(batch=-1), _SHAPE_),
+    (dict(code_dim=0), _UNSUP_), (dict(code_dim=5), _UNSUP_),
+    (dict(feature_samples=33), _UNSUP_),                                   # S^2 = 1089 > 1024
+    (dict(workspace=_Off(8)), _MISAL_),
+    (dict(), _SMALL_),
+    (dict(code_dim=5, workspace_bytes=0), _UNSUP_),
+    (dict(feature_samples=33, workspace=_Off(8)), _UNSUP_),
+    (dict(feats=None, feat_h=0), _NULL_),
+]
+_LOSS_REFUSALS = {
+    "nsos_geo_correlation_loss": _GEO_COMMON + [
+        (dict(batch=-1), _SHAPE_), (dict(loss=None), _NULL_),
+    ] + [({k: None}, _NULL_) for k in ("depth", "code", "ray_o", "ray_d", "neg", "workspace")],
+    "nsos_geo_correlation_loss_rows": _GEO_ROWS_COMMON + [
+        (dict(batch=-1), _SHAPE_), (dict(n_rows=3), _SHAPE_),
+        (dict(batch=-1, phase=4), _UNSUP_),                                # the phase before the batch ...
+    ] + [({k: None}, _NULL_) for k in ("depth", "code", "ray_o", "ray_d", "neg", "workspace")],
+    "nsos_geo_correlation_loss_pair": _GEO_ROWS_COMMON + [
+        (dict(grad1=None), _SMALL_),
+        (dict(batch=-1), _SHAPE_), (dict(n_rows=4), _SMALL_), (dict(n_rows=5), _SHAPE_),     # two code maps: 2 * batch row patches
+        (dict(batch=-1, phase=4), _SHAPE_),                                # ... here the batch before the phase
+    ] + [({k: None}, _NULL_) for k in ("depth", "code", "code1", "ray_o", "ray_d", "neg", "workspace")],
+    "nsos_app_correlation_loss": _APP_COMMON + [(dict(loss=None), _NULL_)]
+                                 + [({k: None}, _NULL_) for k in ("feats", "code", "neg", "rand1", "rand2", "workspace")],
+    "nsos_app_correlation_loss_nhwc": _APP_COMMON + [(dict(loss=None), _NULL_)]
+                                      + [({k: None}, _NULL_) for k in ("feats", "code", "neg", "rand1", "rand2", "workspace")],
+    "nsos_app_correlation_loss_rows": _APP_COMMON + _ROWS_COMMON + [
+        (dict(phase=3), _UNSUP_), (dict(n_rows=3), _SHAPE_),
+        (dict(phase=3, feats=None), _UNSUP_),                              # two faults: the phase first, then -- unlike the geometric
+        (dict(exchange_means=_Off(4), feats=None), _NULL_),                # entries -- pointers, shapes and limits, and only then the
+        (dict(exchange_sums=_Off(2), rows=None), _NULL_),                  # alignment of workspace and exchange buffers together
+        (dict(exchange_means=_Off(4), code_dim=5), _UNSUP_),
+        (dict(exchange_means=_Off(4), n_rows=3), _SHAPE_),
+        (dict(batch=-1, phase=3), _UNSUP_),
+    ] + [({k: None}, _NULL_) for k in ("feats", "code", "neg", "rand1", "rand2", "workspace")],
+}
+
+
+def test_loss_entry_points_report_the_same_fault_first():
+    """All six correlation-loss entry points: every single way of getting a call wrong, and pairs of faults (which pin the ORDER of the
+    checks).  Validation precedes any HIP call: nothing is launched, no device is needed."""
+    lib = _lib.lib()
+    buf = (C.c_double * 8)()
+    base_ptr = C.cast(buf, C.c_void_p).value
+    assert base_ptr % 16 == 0
+    assert set(_LOSS_REFUSALS) == set(_LOSS_ENTRIES)
+    n = 0
+    for name, argnames in _LOSS_ENTRIES.items():
+        geo, pair = "geo" in name, name.endswith("_pair")
+        full = (lib.nsos_corr_workspace_bytes(1, 4 if pair else 2, 64, 0) if geo else lib.nsos_corr_workspace_bytes(0, 2, 121, 7))
+        assert full > 0
+
+        def call(change):
+            vals = dict(_LOSS_BASE, phase=_LAST_PHASE.get(name, 0), workspace_bytes=full - 1)
+            vals.update(change)
+            args = []
+            for a in argnames:
+                v = vals.get(a, _Off(0))
+                args.append(C.c_void_p(base_ptr + v) if isinstance(v, _Off) else v)
+            return getattr(lib, name)(*args)
+
+        for change, want in _LOSS_REFUSALS[name]:
+            assert call(change) == want, (name, change, want)
+            n += 1
+        # an empty batch is no work: accepted whatever else the call holds
+        empty = {a: (None if a not in _LOSS_BASE and a not in ("phase", "workspace_bytes") else 0) for a in argnames}
+        empty.update(code_dim=5, phase=9, n_rows=7, stream=None)
+        assert call({k: v for k, v in empty.items() if k in argnames}) == 0, name
+    assert n > 150

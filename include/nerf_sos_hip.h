@@ -560,7 +560,8 @@ int32_t nsos_composite_importance(const float* raw, const float* z_vals, const f
  * order, rand[R,S] (stratified jitter, models/sampler.py:61), randn[R,S] (coarse sigma noise, models/renderer.py:47),
  * rand[R,N] (importance u, models/sampler.py:103), randn[R,S+N] (fine sigma noise) from torch's global generator: four
  * launches.  Here a counter-based Philox4x32-10 stream keyed by `seed`, advanced by `call` (one value per chunk / step),
- * fills whichever of the four buffers is not NULL.  NOT torch's values: the default path keeps torch's generator so that
+ * fills whichever of the four buffers is not NULL: element e of the padded concatenation is word e & 3 of block e >> 2; a uniform is
+ * (k + 0.5) 2^-23 over its word's top 23 bits (never 0 or 1), normals are Box-Muller pairs of two such uniforms.  NOT torch's values: the default path keeps torch's generator so that
  * the reference's captured draws can be injected (tests/golden/end_to_end.npz). */
 int32_t nsos_render_draws(uint64_t seed, uint64_t call, int64_t n_rays, int32_t n_coarse, int32_t n_importance,
                           float* t_rand, float* noise0, float* u, float* noise1, void* stream);

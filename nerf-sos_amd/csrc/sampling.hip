@@ -115,8 +115,8 @@ __global__ __launch_bounds__(128) void importance_wide_kernel(const float* __res
 // sigma noise, rand[R,N] importance u, randn[R,S+N] fine sigma noise: models/sampler.py:61,103, models/renderer.py:47) --
 // four generator launches plus their bookkeeping on the host.  This kernel fills all four in ONE launch from a
 // counter-based generator (Philox4x32-10, the generator behind torch's own CUDA/HIP streams): element e of the
-// concatenated stream is word (e & 3) of block e >> 2 under key = seed, counter = (block, call).  Uniforms are 24-bit
-// (k + 0.5) 2^-24 in (0,1); normals are Box-Muller pairs.  Opt-in (NeRFNet.rng = "philox"): the values are NOT torch's, so
+// concatenated stream is word (e & 3) of block e >> 2 under key = seed, counter = (block, call).  Uniforms are 23-bit
+// (k + 0.5) 2^-23 in (0,1), k the word's top 23 bits; normals are Box-Muller pairs.  Opt-in (NeRFNet.rng = "philox"): the values are NOT torch's, so
 // the parity tests (which inject the reference's captured draws) keep the default path.
 struct Philox {
     unsigned key[2];
@@ -131,7 +131,9 @@ struct Philox {
         for (int i = 0; i < 10; ++i) { round(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
     }
 };
-__device__ __forceinline__ float u01(unsigned x) { return ((float)(x >> 8) + 0.5f) * 5.9604644775390625e-08f; }   // (0,1)
+// k < 2^23: k + 0.5 and the product are exact in fp32, the range is [2^-24, 1 - 2^-24].  (24 bits would not do: k + 0.5 is a tie for
+// every k >= 2^23 and rounds to exactly 1.0 at k = 2^24 - 1.)
+__device__ __forceinline__ float u01(unsigned x) { return ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f; }
 
 __global__ __launch_bounds__(256) void render_draws_kernel(unsigned long long seed, unsigned long long call,
                                                            long long n_uniform0, long long n_normal0, long long n_uniform1,

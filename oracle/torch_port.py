@@ -285,7 +285,7 @@ def composite(raw: Tensor, z_vals: Tensor, rays_d: Tensor, noise: Optional[Tenso
     """models/renderer.py:35-85.  ``noise`` is the already-scaled additive sigma noise
     (``randn * raw_noise_std``) or None."""
     dists = z_vals[..., 1:] - z_vals[..., :-1]
-    dists = torch.cat([dists, 1e10 * torch.ones_like(dists[..., :1])], -1)
+    dists = torch.cat([dists, 1e10 * torch.ones_like(z_vals[..., :1])], -1)   # (shaped by z_vals: a single sample has no dists[..., :1])
     dists = dists * torch.linalg.norm(rays_d[..., None, :], ord=2, dim=-1)
     rgb = torch.sigmoid(raw[..., :3])
     sigma = raw[..., 3] + (noise if noise is not None else 0.0)

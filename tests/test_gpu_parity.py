@@ -1129,7 +1129,7 @@ def test_lp8_equals_lp4_bitwise(manifest, name, precision):
 # ------------------------------------------------------------------------------------------ train-mode draws in one launch
 def test_philox_render_draws():
     """nsos_render_draws: the four train-mode random tensors of a ray chunk from one counter-based launch.  Checked:
-    ranges, moments (24-bit uniforms in (0,1); Box-Muller normals), independence of the four tensors and of consecutive
+    ranges, moments (23-bit uniforms in (0,1); Box-Muller normals), independence of the four tensors and of consecutive
     calls, reproducibility by (seed, call), odd sizes (tail blocks of 4), and the module option NeRFNet.rng = 'philox'."""
     R, S, N = 4099, 64, 128
     t, n0, u, n1 = ops.render_draws(1234, 1, R, S, N, DEV)

@@ -34,7 +34,8 @@ extern "C" {
  * nsos_ssim, nsos_adjusted_rand, nsos_kmeans; 10: the DINO ViT-S/16 feature extractor nsos_dino_*).  The folded fp32 stream
  * (nsos_mlp_pack_fold / nsos_mlp_*_fold) only ADDS entry points -- no existing argument list or buffer format moved, so the version
  * stands; a library without them fails to bind (every declared symbol is resolved at load) and reports another source hash.  The same
- * holds for LPIPS (nsos_lpips_*): four new entry points, nothing existing moved -- and for the camera layer (nsos_camera_*): three. */
+ * holds for LPIPS (nsos_lpips_*): four new entry points, nothing existing moved -- for the camera layer (nsos_camera_*): three -- and for
+ * DINO's backward to the input (nsos_dino_forward_save, nsos_dino_backward and their four size / pack functions). */
 #define NSOS_ABI_VERSION 10
 
 enum {
@@ -756,7 +757,7 @@ int32_t nsos_geo_correlation_loss(float* depth, const float* code, const float* 
                                   float neg_weight, float max_depth, int32_t filter_in_place, float* loss,
                                   float* grad_code, void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- DINO ViT-S/16 feature extractor (forward only, fp32) ----------------------------------------------------------
+/* ---- DINO ViT-S/16 feature extractor (fp32; its backward: below) ----------------------------------------------------------
  * What engines/trainer.py:101-109 runs between the render and the losses: the rendered patches through a frozen DINO
  * ViT-S/16 (models/extractor.py:204-213 get_vit_attn_feat over models/vision_transformer.py vit_small(patch_size=16)).
  *   1. engines/trainer.py:103-106: channels first, F.interpolate(x, (h*stride, w*stride)) (nearest), (x - mean) / std;
@@ -823,6 +824,48 @@ int32_t nsos_dino_forward(const float* input, int32_t batch, int32_t in_h, int32
 /* Host helper: the source index of each of the 224 output rows (or columns) of steps 1-2 for an input extent `in_size`
  * (patch_stride <= 0: step 2 alone), exactly the rule the prepare kernel evaluates.  idx: HOST int32 [224]. */
 int32_t nsos_dino_resize_indices(int32_t in_size, int32_t patch_stride, int32_t* idx);
+
+/* ---- DINO ViT-S/16, backward to the input (csrc/dino_vit_bwd.hip; fp32) ---------------------------------------------------------------
+ * The gradient of sum(feat * g_feat) + sum(cls * g_cls) with respect to the image handed to nsos_dino_forward: the reference's
+ * extractor is differentiable (engines/trainer.py:103-108 feeds the rendered rgb to it with autograd on), the weights are frozen, so
+ * input gradients only.
+ *   nsos_dino_forward_save  = nsos_dino_forward (same launches, bit-equal feat / cls / attn; no `prepared`, no `blocks`) that also keeps
+ *     the input of every block: saved [12][B][197][384], nsos_dino_saved_bytes(batch) = 3.63 MB per image (0 for a batch outside
+ *     1..NSOS_DINO_MAX_BATCH), 16-byte aligned.  Checks as nsos_dino_forward, `saved` joining the NULL and the alignment check.
+ *   nsos_dino_pack_backward: the backward's own stream, nsos_dino_backward_packed_bytes() bytes, 16-byte aligned: 1536 zeros, then
+ *     patch_embed.proj.weight and every block's qkv / proj / fc1 / fc2 matrix in the state dict's own [out,in] layout (the operand of
+ *     dA[M,in] = dOut[M,out] . W[out,in] on the forward's GEMM tile).  Checks as nsos_dino_pack; sets the backward kernels' per-device
+ *     attribute (and the forward's), so that a first nsos_dino_backward inside a stream capture has nothing left to configure.
+ *   nsos_dino_backward: batch / in_h / in_w / patch_stride / flags as given to the forward; packed (nsos_dino_pack) and packed_bwd
+ *     (nsos_dino_pack_backward) of the same checkpoint; saved from nsos_dino_forward_save of that call; g_feat [B,196,384] and g_cls [B,384],
+ *     either may be NULL (= zeros, bit for bit), not both; workspace nsos_dino_backward_workspace_bytes(batch) bytes (4.25 MB per image, 0
+ *     for a batch outside 1..NSOS_DINO_MAX_BATCH), 16-byte aligned; g_input: the input's shape and layout ([B,h,w,3] with
+ *     NSOS_DINO_NHWC, else [B,3,h,w]), every element written -- a source pixel that no pixel of the 224 x 224 image reads (an input
+ *     larger than 224) gets exactly 0.0; g_blocks (optional, NULL to skip): the residual-stream gradient at the INPUT of every block,
+ *     [12][B][197][384], the mirror of `blocks`.
+ *     Per block, 11..0: the block's forward is recomputed from its saved input with the forward's kernels (qkv, the residual midpoint,
+ *     the MLP's pre-activation), then fc2 -> GELU' (exact erf form) -> fc1 -> LayerNorm' -> proj -> attention' (probabilities recomputed)
+ *     -> qkv -> LayerNorm'; then the patch embedding and the two resizes as one gather, * 1/sd_c (1/sd_c^2 with NSOS_DINO_STEP1, 1 with
+ *     NSOS_DINO_PREPARED).
+ *     Check order: NULL pointer (packed, packed_bwd, saved, workspace, g_input, and g_feat and g_cls both NULL) -> then exactly
+ *     nsos_dino_forward's: shape -> flag bits -> PREPARED -> STEP1 -> size limits -> alignment (16 bytes: packed, packed_bwd, saved,
+ *     workspace; 4: g_feat, g_cls, g_input, g_blocks) -> workspace size.  Everything is validated before anything is launched or written.
+ *     No host synchronisation, no allocation: capturable.
+ *     Order (fixed; no atomics; an image's bits do not depend on its batch): every data-gradient GEMM output is one fp32 fma chain over
+ *     the out-features ascending from 0 (v_mfma_f32_32x32x2_f32); LayerNorm' row sums as the forward's; attention (v_mfma_f32_16x16x4_f32):
+ *     p as the forward, dP = dO.v over d ascending, delta = rowsum(dP*p) (four strided columns per lane ascending, then the butterfly),
+ *     dQ over the keys ascending, dK and dV over the queries ascending in one workgroup per 32 keys; the input gather sums a pixel's
+ *     preimage in ascending (y, x) order. */
+size_t nsos_dino_saved_bytes(int32_t batch);
+int32_t nsos_dino_forward_save(const float* input, int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags,
+                               const void* packed, void* workspace, size_t workspace_bytes, float* feat, float* cls, float* attn,
+                               float* saved, void* stream);
+size_t nsos_dino_backward_packed_bytes(void);
+int32_t nsos_dino_pack_backward(const nsos_dino_tensors* tensors, void* packed_bwd, size_t packed_bytes, void* stream);
+size_t nsos_dino_backward_workspace_bytes(int32_t batch);
+int32_t nsos_dino_backward(int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags, const void* packed,
+                           const void* packed_bwd, const float* saved, const float* g_feat, const float* g_cls, void* workspace,
+                           size_t workspace_bytes, float* g_input, float* g_blocks, void* stream);
 
 /* ---- DINO ViT-S/16, 16-bit operands (csrc/dino_vit16.hip) ---------------------------------------------------------------------
  * The same forward pass as nsos_dino_forward (same arguments, flags, outputs -- all fp32 -- and validation) with the two operands of

@@ -164,6 +164,12 @@ SIGNATURES = {
     "nsos_dino_workspace_bytes": (_sz, [_i32]),
     "nsos_dino_forward": (_i32, [_fp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _fp]),
     "nsos_dino_resize_indices": (_i32, [_i32, _i32, C.POINTER(C.c_int32)]),
+    "nsos_dino_saved_bytes": (_sz, [_i32]),
+    "nsos_dino_forward_save": (_i32, [_fp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _sz, _fp, _fp, _fp, _fp, _fp]),
+    "nsos_dino_backward_packed_bytes": (_sz, []),
+    "nsos_dino_pack_backward": (_i32, [C.POINTER(DinoTensors), _fp, _sz, _fp]),
+    "nsos_dino_backward_workspace_bytes": (_sz, [_i32]),
+    "nsos_dino_backward": (_i32, [_i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _sz, _fp, _fp, _fp]),
     "nsos_dino_packed16_bytes": (_sz, []),
     "nsos_dino_pack16": (_i32, [C.POINTER(DinoTensors), _i32, _fp, _sz, _fp]),
     "nsos_dino_workspace16_bytes": (_sz, [_i32]),

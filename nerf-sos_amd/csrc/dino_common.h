@@ -100,10 +100,12 @@ inline int32_t dino_check_tensors(const nsos_dino_tensors* t) {
 }
 // nsos_dino_forward / nsos_dino_forward16: NULL pointer -> shape -> flag bits -> [precision] -> PREPARED -> STEP1 -> size limits ->
 // alignment -> workspace size.  `need` is the entry point's own workspace-bytes function; fp32 has no precision to refuse.
+// nsos_dino_backward takes the same path with its input GRADIENT in the place of `input`; what it has of further pointers joins the NULL
+// check (`others`) and the alignment check (`others_aligned`) at their places in the order.
 inline int32_t dino_check_forward(const float* input, int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags,
                                   const void* packed, const void* workspace, size_t workspace_bytes, size_t (*need)(int32_t),
-                                  bool precision_ok = true) {
-    NSOS_REQUIRE(input && packed && workspace, NSOS_ERR_NULL_POINTER);
+                                  bool precision_ok = true, bool others = true, bool others_aligned = true) {
+    NSOS_REQUIRE(input && packed && workspace && others, NSOS_ERR_NULL_POINTER);
     NSOS_REQUIRE(batch > 0 && in_h > 0 && in_w > 0, NSOS_ERR_BAD_SHAPE);
     NSOS_REQUIRE((flags & ~7) == 0, NSOS_ERR_UNSUPPORTED);
     NSOS_REQUIRE(precision_ok, NSOS_ERR_UNSUPPORTED);
@@ -116,7 +118,8 @@ inline int32_t dino_check_forward(const float* input, int32_t batch, int32_t in_
         NSOS_REQUIRE(patch_stride <= (1 << 10), NSOS_ERR_UNSUPPORTED);
     }
     NSOS_REQUIRE(batch <= NSOS_DINO_MAX_BATCH && in_h <= (1 << 14) && in_w <= (1 << 14), NSOS_ERR_UNSUPPORTED);
-    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)input & 3) == 0, NSOS_ERR_MISALIGNED);
+    NSOS_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)input & 3) == 0 && others_aligned,
+                 NSOS_ERR_MISALIGNED);
     NSOS_REQUIRE(workspace_bytes >= need(batch), NSOS_ERR_BUFFER_TOO_SMALL);
     return NSOS_OK;
 }

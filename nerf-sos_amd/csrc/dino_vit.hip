@@ -1,4 +1,5 @@
-// DINO ViT-S/16 feature extractor, forward only, fp32 (include/nerf_sos_hip.h "DINO ViT-S/16").
+// DINO ViT-S/16 feature extractor, the forward, fp32 (include/nerf_sos_hip.h "DINO ViT-S/16").  Its backward to the
+// input image is dino_vit_bwd.hip; dino_layout32.h holds what the two share.
 // Replaces engines/trainer.py:103-106 (resize + normalize_batch), models/extractor.py:204-213 (get_vit_attn_feat) and
 // models/vision_transformer.py:196-215 (vit_small(patch_size=16): prepare_tokens + 12 blocks) with four kernels:
 //   dino_prepare_kernel   steps 1-2 (two nearest resizes as one gather, two normalisations) fused with the patch embedding's im2col
@@ -14,27 +15,12 @@
 #include "mlp_common.h"
 #include "dino_common.h"
 #include "gemm32_tile.h"
+#include "dino_layout32.h"   // the packed stream and the workspace (shared with dino_vit_bwd.hip)
 
 namespace {
 
 using namespace nsos::dino;   // geometry, resize index rule, prepared pixel, wave reductions: dino_common.h
-
-// ---- packed stream (floats) ----------------------------------------------------------------------------------------------------
-constexpr size_t P_POS = 0;                                  // [197][384], row 0 = cls_token + pos_embed[0]
-constexpr size_t P_EMB_W = P_POS + (size_t)T * D;            // [768][384]  (patch_embed.proj.weight transposed)
-constexpr size_t P_EMB_B = P_EMB_W + (size_t)KE * D;
-constexpr size_t P_BLOCKS = P_EMB_B + D;
-constexpr size_t B_LN1W = 0, B_LN1B = B_LN1W + D, B_QKVW = B_LN1B + D, B_QKVB = B_QKVW + (size_t)D * 3 * D, B_PROJW = B_QKVB + 3 * D,
-                 B_PROJB = B_PROJW + (size_t)D * D, B_LN2W = B_PROJB + D, B_LN2B = B_LN2W + D, B_FC1W = B_LN2B + D,
-                 B_FC1B = B_FC1W + (size_t)D * HID, B_FC2W = B_FC1B + HID, B_FC2B = B_FC2W + (size_t)HID * D, B_SIZE = B_FC2B + D;
-constexpr size_t P_SIZE = P_BLOCKS + (size_t)NSOS_DINO_DEPTH * B_SIZE;
-static_assert(P_EMB_W % 4 == 0 && P_BLOCKS % 4 == 0 && B_SIZE % 4 == 0 && B_QKVW % 4 == 0 && B_FC2W % 4 == 0, "float4 rows");
-
-// ---- workspace (floats per image) ----------------------------------------------------------------------------------------------
-constexpr size_t W_X = 0, W_LN = W_X + (size_t)T * D, W_QKV = W_LN + (size_t)T * D, W_AO = W_QKV + (size_t)T * 3 * D,
-                 W_HID = W_AO + (size_t)T * D, W_TOK = W_HID + (size_t)T * HID, W_ROW0 = W_TOK + (size_t)NP * KE,
-                 W_SIZE = W_ROW0 + (size_t)HEADS * NP;
-static_assert(W_SIZE % 4 == 0 && W_LN % 4 == 0 && W_QKV % 4 == 0 && W_TOK % 4 == 0, "16-byte aligned sections for every batch size");
+using namespace nsos::dino32;
 
 // ---- prepare: tokens[b*196 + t][c*256 + py*16 + px] = prepared[b][c][16*ty + py][16*tx + px]; also x[b][0][:] = cls + pos[0] ----
 __global__ __launch_bounds__(256) void dino_prepare_kernel(const float* __restrict__ in, int batch, int in_h, int in_w, int stride, int flags,
@@ -578,11 +564,10 @@ extern "C" int32_t nsos_dino_pack(const nsos_dino_tensors* t, void* packed, size
     return nsos_launch_status();
 }
 
-extern "C" int32_t nsos_dino_forward(const float* input, int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags,
-                                     const void* packed, void* workspace, size_t workspace_bytes, float* feat, float* cls, float* attn,
-                                     float* prepared, float* blocks, void* stream) {
-    if (int32_t c = dino_check_forward(input, batch, in_h, in_w, patch_stride, flags, packed, workspace, workspace_bytes, nsos_dino_workspace_bytes))
-        return c;
+// nsos_dino_forward (saved == nullptr: exactly its launches) and nsos_dino_forward_save (saved[i] = the input of block i)
+static int32_t dino_forward32(const float* input, int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags,
+                              const void* packed, void* workspace, float* feat, float* cls, float* attn, float* prepared, float* blocks,
+                              float* saved, void* stream) {
     if (int32_t c = dino_configure()) return c;
     hipStream_t st = (hipStream_t)stream;
     const float* p = (const float*)packed;
@@ -597,6 +582,8 @@ extern "C" int32_t nsos_dino_forward(const float* input, int32_t batch, int32_t 
     launch_gemm<EPI_EMBED, KE>(tok, p + P_EMB_W, p + P_EMB_B, x, p + P_POS, batch * NP, D, st);
     for (int i = 0; i < NSOS_DINO_DEPTH; ++i) {
         const float* q = p + P_BLOCKS + (size_t)i * B_SIZE;
+        if (saved)
+            dino_copy_kernel<dino32_path><<<blocks_for((long long)M * D), 256, 0, st>>>(x, saved + (size_t)i * M * D, (long long)M * D);
         dino_layernorm_kernel<<<(M + 3) / 4, 256, 0, st>>>(x, q + B_LN1W, q + B_LN1B, ln, M);
         launch_gemm<EPI_BIAS, D>(ln, q + B_QKVW, q + B_QKVB, qkv, nullptr, M, 3 * D, st);
         dino_attention_kernel<<<dim3((T + QT - 1) / QT, HEADS, batch), 256, ATT_LDS_BYTES, st>>>(
@@ -612,6 +599,37 @@ extern "C" int32_t nsos_dino_forward(const float* input, int32_t batch, int32_t 
         dino_outputs_kernel<dino32_path><<<blocks_for((long long)M * D), 256, 0, st>>>(x, attn ? row0 : nullptr, batch, feat, cls,
                                                                                        attn);
     return nsos_launch_status();
+}
+
+extern "C" int32_t nsos_dino_forward(const float* input, int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags,
+                                     const void* packed, void* workspace, size_t workspace_bytes, float* feat, float* cls, float* attn,
+                                     float* prepared, float* blocks, void* stream) {
+    if (int32_t c = dino_check_forward(input, batch, in_h, in_w, patch_stride, flags, packed, workspace, workspace_bytes, nsos_dino_workspace_bytes))
+        return c;
+    return dino_forward32(input, batch, in_h, in_w, patch_stride, flags, packed, workspace, feat, cls, attn, prepared, blocks, nullptr, stream);
+}
+
+extern "C" int32_t nsos_dino_forward_save(const float* input, int32_t batch, int32_t in_h, int32_t in_w, int32_t patch_stride, int32_t flags,
+                                          const void* packed, void* workspace, size_t workspace_bytes, float* feat, float* cls, float* attn,
+                                          float* saved, void* stream) {
+    if (int32_t c = dino_check_forward(input, batch, in_h, in_w, patch_stride, flags, packed, workspace, workspace_bytes, nsos_dino_workspace_bytes,
+                                       true, saved != nullptr, ((uintptr_t)saved & 15) == 0))
+        return c;
+    return dino_forward32(input, batch, in_h, in_w, patch_stride, flags, packed, workspace, feat, cls, attn, nullptr, nullptr, saved, stream);
+}
+
+// ---- for dino_vit_bwd.hip (dino_layout32.h) ------------------------------------------------------------------------------------
+int32_t nsos::dino32::configure() { return dino_configure(); }
+
+void nsos::dino32::recompute_block(const float* q, const float* x_in, float* xmid, float* ln, float* qkv, float* ao, float* hid, int batch,
+                                   hipStream_t st) {
+    const int M = batch * T;
+    dino_layernorm_kernel<<<(M + 3) / 4, 256, 0, st>>>(x_in, q + B_LN1W, q + B_LN1B, ln, M);
+    launch_gemm<EPI_BIAS, D>(ln, q + B_QKVW, q + B_QKVB, qkv, nullptr, M, 3 * D, st);
+    dino_attention_kernel<<<dim3((T + QT - 1) / QT, HEADS, batch), 256, ATT_LDS_BYTES, st>>>(qkv, ao, nullptr);
+    launch_gemm<EPI_RESIDUAL, D>(ao, q + B_PROJW, q + B_PROJB, xmid, x_in, M, D, st);
+    dino_layernorm_kernel<<<(M + 3) / 4, 256, 0, st>>>(xmid, q + B_LN2W, q + B_LN2B, ln, M);
+    launch_gemm<EPI_BIAS, D>(ln, q + B_FC1W, q + B_FC1B, hid, nullptr, M, HID, st);
 }
 
 // ---- full-image path -----------------------------------------------------------------------------------------------------------

@@ -87,6 +87,8 @@ class GraphedPatchStep:
     the captured call packs nothing, allocates nothing and never synchronises; the graph holds the packed stream's and the
     workspace's addresses, so change the extractor's weights or `precision` only together with a new capture.  DinoViT keeps ONE
     workspace per device: do not call the same DinoViT from another stream while a replay is in flight (dino.DinoViT._ws).
+    The extractor's backward to the render (sharding.sharded_patch_step(dino_grad=True)) is NOT wired into the captured step: the
+    extractor here writes through `out=` and is forward-only, so `cls` reaches the contrastive term detached.
     `eager_step()` runs the very same function without the graph (same generator, same counter): replay k and eager step k
     produce the same bits (tests/test_gpu_sharded.py).
 

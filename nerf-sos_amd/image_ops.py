@@ -92,10 +92,14 @@ def _dino_pack(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor], p
     for i in range(DINO_DEPTH):
         for field, name in _DINO_BLOCK_FIELDS:
             setattr(ts.blocks[i], field, ptr(f"blocks.{i}.{name}"))
-    packed = table.packed(packed, int(_lib.lib().nsos_dino_packed_bytes() if precision == "fp32" else _lib.lib().nsos_dino_packed16_bytes()))
+    L = _lib.lib()
+    nbytes = {"fp32": L.nsos_dino_packed_bytes, "backward": L.nsos_dino_backward_packed_bytes}.get(precision, L.nsos_dino_packed16_bytes)()
+    packed = table.packed(packed, int(nbytes))
     with torch.cuda.device(packed.device):
         if precision == "fp32":
             _lib.check(_lib.lib().nsos_dino_pack(C.byref(ts), _p(packed), packed.numel() * 4, _stream()), "nsos_dino_pack")
+        elif precision == "backward":
+            _lib.check(L.nsos_dino_pack_backward(C.byref(ts), _p(packed), packed.numel() * 4, _stream()), "nsos_dino_pack_backward")
         else:
             _lib.check(_lib.lib().nsos_dino_pack16(C.byref(ts), DTYPES[precision], _p(packed), packed.numel() * 4, _stream()),
                        "nsos_dino_pack16")
@@ -105,6 +109,12 @@ def _dino_pack(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor], p
 def dino_pack(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor] = None) -> torch.Tensor:
     """DINO's checkpoint tensors (state-dict names, on one GPU) -> the stream nsos_dino_forward reads (`nsos_dino_pack`)."""
     return _dino_pack(state, packed, "fp32")
+
+
+def dino_pack_backward(state: Dict[str, torch.Tensor], packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`nsos_dino_pack_backward`: the stream nsos_dino_backward reads beside dino_pack's -- the matrices in the state dict's own
+    [out,in] layout, the operand of the data-gradient GEMMs."""
+    return _dino_pack(state, packed, "backward")
 
 
 DINO_PRECISIONS = ("fp32", "fp16", "bf16")
@@ -157,7 +167,10 @@ def _dino_out(out, batch: int) -> None:
             raise ValueError(f"dino: out['{name}'] must be contiguous (strides {t.stride()}): the kernels write it densely")
 
 
-def _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, precision, out=None) -> Dict[str, torch.Tensor]:
+def _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, precision, out=None,
+                  saved=None) -> Dict[str, torch.Tensor]:
+    if saved is not None and (precision != "fp32" or want_prepared or want_blocks):
+        raise ValueError("dino: saved= (nsos_dino_forward_save) is the fp32 forward without `prepared` / `blocks`")
     if out is not None:
         if not isinstance(x, torch.Tensor) or x.dim() != 4:
             raise ValueError(f"dino: expected a 4-d image batch, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
@@ -172,6 +185,8 @@ def _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_pre
         workspace = _empty(ws_floats(B), dev)
     _buffer(packed, "dino", "packed", int(L.nsos_dino_packed_bytes() if f32 else L.nsos_dino_packed16_bytes()), dev)
     _buffer(workspace, "dino", "workspace", ws_floats(B) * 4, dev)
+    if saved is not None:
+        _buffer(saved, "dino", "saved", dino_saved_floats(B) * 4, dev)
     if out is not None:
         for name in ("feat", "cls_"):
             if out[name].device != dev:
@@ -188,7 +203,11 @@ def _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_pre
         out["blocks"] = torch.empty((DINO_DEPTH, B, DINO_TOKENS, DINO_WIDTH), device=dev, dtype=torch.float32)
     outs = (_p(out["feat"]), _p(out["cls_"]), _p(out.get("attn")), _p(out.get("prepared")), _p(out.get("blocks")), _stream())
     with torch.cuda.device(dev):
-        if f32:
+        if saved is not None:
+            _lib.check(L.nsos_dino_forward_save(_p(x), B, h, w, int(patch_stride), int(flags), _p(packed), _p(workspace),
+                                                workspace.numel() * 4, _p(out["feat"]), _p(out["cls_"]), _p(out.get("attn")), _p(saved),
+                                                _stream()), "nsos_dino_forward_save")
+        elif f32:
             _lib.check(L.nsos_dino_forward(_p(x), B, h, w, int(patch_stride), int(flags), _p(packed), _p(workspace), workspace.numel() * 4,
                                            *outs), "nsos_dino_forward")
         else:
@@ -199,12 +218,69 @@ def _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_pre
 
 def dino_forward(x: torch.Tensor, packed: torch.Tensor, flags: int, patch_stride: int = 0, workspace: Optional[torch.Tensor] = None,
                  want_attn: bool = True, want_prepared: bool = False, want_blocks: bool = False,
-                 out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+                 out: Optional[Dict[str, torch.Tensor]] = None, saved: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """`nsos_dino_forward`: x [B,h,w,3] (DINO_NHWC) or [B,3,h,w] -> {'feat' [B,196,384], 'cls_' [B,384], 'attn' [B,1,196]}
     (+ 'prepared' [B,3,224,224], 'blocks' [12,B,197,384] on request).  Launches only; capturable.
     out={"feat": ..., "cls_": ...}: contiguous float32 tensors of exactly those shapes on x's device that the kernels write instead of
-    fresh ones (ValueError otherwise); the returned dict holds them.  With want_attn=False such a call allocates nothing."""
-    return _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, "fp32", out)
+    fresh ones (ValueError otherwise); the returned dict holds them.  With want_attn=False such a call allocates nothing.
+    saved= (a buffer of dino_saved_floats(B) floats): `nsos_dino_forward_save` instead -- the same launches and the same output bits,
+    and the input of every block kept in `saved` [12,B,197,384] for dino_backward."""
+    return _dino_forward(x, packed, flags, patch_stride, workspace, want_attn, want_prepared, want_blocks, "fp32", out, saved)
+
+
+def dino_saved_floats(batch: int) -> int:
+    return _floats(_lib.lib().nsos_dino_saved_bytes(int(batch)), f"dino: batch size {batch} outside what the kernels take")
+
+
+def dino_backward_workspace_floats(batch: int) -> int:
+    return _floats(_lib.lib().nsos_dino_backward_workspace_bytes(int(batch)), f"dino: batch size {batch} outside what the kernels take")
+
+
+def dino_backward_workspace(batch: int, device) -> torch.Tensor:
+    return _empty(dino_backward_workspace_floats(batch), device)
+
+
+def dino_backward(shape, flags: int, patch_stride: int, packed: torch.Tensor, packed_bwd: torch.Tensor, saved: torch.Tensor,
+                  g_feat: Optional[torch.Tensor], g_cls: Optional[torch.Tensor], workspace: Optional[torch.Tensor] = None,
+                  want_g_blocks: bool = False) -> Dict[str, torch.Tensor]:
+    """`nsos_dino_backward`: the gradient of sum(feat * g_feat) + sum(cls_ * g_cls) with respect to the image of a dino_forward(...,
+    saved=saved) call.  shape: that image's shape ([B,h,w,3] with DINO_NHWC in `flags`, else [B,3,h,w]); flags / patch_stride as given
+    to the forward; packed from dino_pack, packed_bwd from dino_pack_backward; g_feat [B,196,384] / g_cls [B,384], either may be None
+    (= zeros), not both.  Returns {'g_input': `shape`} (+ 'g_blocks' [12,B,197,384], the residual-stream gradient at every block's
+    input, on request).  Launches only; capturable."""
+    L = _lib.lib()
+    if g_feat is None and g_cls is None:
+        raise ValueError("dino: dino_backward needs g_feat or g_cls")
+    first = g_feat if g_feat is not None else g_cls
+    g_feat = None if g_feat is None else _dev(g_feat, "g_feat")
+    g_cls = None if g_cls is None else _dev(g_cls, "g_cls")
+    dev = first.device
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != 4:
+        raise ValueError(f"dino: expected the shape of a 4-d image batch, got {shape}")
+    nhwc = bool(flags & DINO_NHWC)
+    B, h, w, ch = (shape[0], shape[1], shape[2], shape[3]) if nhwc else (shape[0], shape[2], shape[3], shape[1])
+    if ch != 3:
+        raise ValueError(f"dino: expected 3 channels, got {shape}")
+    for t, name, want in ((g_feat, "g_feat", (B, DINO_TOKENS - 1, DINO_WIDTH)), (g_cls, "g_cls", (B, DINO_WIDTH))):
+        if t is not None and tuple(t.shape) != want:
+            raise ValueError(f"dino: `{name}` has shape {tuple(t.shape)}, the gradient of that output is {want}")
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"dino: `{name}` is on {t.device}, the data on {dev}")
+    if workspace is None:
+        workspace = dino_backward_workspace(B, dev)
+    _buffer(packed, "dino", "packed", int(L.nsos_dino_packed_bytes()), dev)
+    _buffer(packed_bwd, "dino", "packed_bwd", int(L.nsos_dino_backward_packed_bytes()), dev)
+    _buffer(saved, "dino", "saved", dino_saved_floats(B) * 4, dev)
+    _buffer(workspace, "dino", "workspace", dino_backward_workspace_floats(B) * 4, dev)
+    out = {"g_input": torch.empty(shape, device=dev, dtype=torch.float32)}
+    if want_g_blocks:
+        out["g_blocks"] = torch.empty((DINO_DEPTH, B, DINO_TOKENS, DINO_WIDTH), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(L.nsos_dino_backward(B, h, w, int(patch_stride), int(flags), _p(packed), _p(packed_bwd), _p(saved), _p(g_feat), _p(g_cls),
+                                        _p(workspace), workspace.numel() * 4, _p(out["g_input"]), _p(out.get("g_blocks")), _stream()),
+                   "nsos_dino_backward")
+    return out
 
 
 def dino_forward16(x: torch.Tensor, packed: torch.Tensor, flags: int, precision: str, patch_stride: int = 0,

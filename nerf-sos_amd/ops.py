@@ -1256,6 +1256,7 @@ from .image_ops import (  # noqa: E402,F401
     DINO_FULL_NHWC, DINO_FULL_NORMALIZE, DINO_FULL_MAX_PATCHES, DINO_PATCH,
     dino_pack, dino_pack16, dino_workspace_floats, dino_workspace, dino_workspace16_floats, dino_workspace16,
     dino_forward, dino_forward16, _dino_forward, dino_resize_indices,
+    dino_pack_backward, dino_saved_floats, dino_backward_workspace_floats, dino_backward_workspace, dino_backward,
     dino_full_workspace_floats, dino_full_workspace, dino_forward_full, dino_interp_pos, dino_find_fg,
     LPIPS_NHWC, LPIPS_NORMALIZE, LPIPS_LAYERS, LPIPS_MIN_SIZE, LPIPS_CHANNELS, LPIPS_CONV_KEYS, _LPIPS_CONV_SHAPES,
     lpips_key_shapes, lpips_feature_sizes, lpips_pack, lpips_workspace_floats, lpips_workspace, lpips_forward)

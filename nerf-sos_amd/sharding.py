@@ -500,7 +500,8 @@ def sharded_patch_step(net, rays: torch.Tensor, bounds, n_patches: int, feat: Op
                        seed: Optional[int] = 0, group=None, timings: Optional[dict] = None,
                        overlap_losses: bool = True, contrast_loss=None, contrast_w: float = 0.0,
                        generator: Optional[torch.Generator] = None, loss_out: Optional[torch.Tensor] = None, *,
-                       dino=None, patch_stride: Optional[int] = None, dino_out: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+                       dino=None, patch_stride: Optional[int] = None, dino_out: Optional[Dict[str, torch.Tensor]] = None,
+                       dino_grad: bool = False) -> torch.Tensor:
     """One patch-mode training step of the path with the patch batch sharded over the ranks -- the loss section of
     `train_one_step` (engines/trainer.py:101-166) re-stated for one process per GPU:
 
@@ -514,7 +515,8 @@ def sharded_patch_step(net, rays: torch.Tensor, bounds, n_patches: int, feat: Op
          O(P^4) geometric one row-partitioned: each rank its own patches' pair sets, four tiny sum-all-reduces
       -> `contrast_loss` (NeRFContrastive, engines/trainer.py:168-170), if given: contrast_w * contrast_loss(cls_) on the
          gathered class tokens -- every rank evaluates the same B x 384 values; its gradient goes to the feature extractor's
-         input, which is outside this path, so under the frozen-backbone recipe it only moves the loss value
+         input: with dino= and dino_grad=True through the extractor into this rank's render, otherwise nowhere (under the
+         frozen-backbone recipe it only moves the loss value)
       -> backward through the rank's own patches -> ONE flat all-reduce (sum) of the parameter gradients.
 
     Returns the (batch-wide) loss; `.grad` of the trainable parameters then holds the single-process gradient.
@@ -528,9 +530,12 @@ def sharded_patch_step(net, rays: torch.Tensor, bounds, n_patches: int, feat: Op
     own step (engines/trainer.py:101-109) -- after the rank's render the step runs
     ``dino.patch_features(ret["rgb"].detach(), patch_stride, want_attn=False)`` on the rank's [n_local,P,P,3] patches as rendered and
     uses its 'feats' / 'cls_tokens' where the caller's tensors went; gather, splice, negatives, both loss paths and the contrastive
-    term are unchanged.  `dino.precision` is honoured as it stands.  A rank that owns no patch does not call the extractor.  The
-    extractor is forward-only: `cls_` reaches `contrast_loss` detached, exactly like a caller-supplied `cls_tokens` -- the gradient
-    into the extractor's input (through it, into the rendered rgb) stays outside this path.  `dino_out` ({"feat": [n_local,196,384],
+    term are unchanged.  `dino.precision` is honoured as it stands.  A rank that owns no patch does not call the extractor.  By
+    default the extractor runs forward-only: `cls_` reaches `contrast_loss` detached, exactly like a caller-supplied `cls_tokens`.
+    `dino_grad=True` (needs dino=, fp32, and excludes dino_out=: ValueError) is the reference's step with a field that is not frozen:
+    the extractor takes ``ret["rgb"]`` undetached with ``differentiable=True``, the rank's own gradient-carrying `cls_` rows are spliced
+    into the gathered batch like its rendered maps, and the contrastive term's gradient runs back through the extractor (HIP kernels,
+    csrc/dino_vit_bwd.hip) into the render.  (The correlation losses still detach `feat`.)  `dino_out` ({"feat": [n_local,196,384],
     "cls_": [n_local,384]}) makes the extractor write into the caller's buffers (DinoViT.patch_features(out=...); what a captured
     step needs to keep its features readable).
 
@@ -540,6 +545,10 @@ def sharded_patch_step(net, rays: torch.Tensor, bounds, n_patches: int, feat: Op
     check_step_features("sharded_patch_step", dino, patch_stride, feat, cls_tokens)
     if dino is None and dino_out is not None:
         raise ValueError("sharded_patch_step: dino_out names the extractor's output buffers -- it means nothing without dino=")
+    if dino_grad and dino is None:
+        raise ValueError("sharded_patch_step: dino_grad=True back-propagates through the step's own extractor -- it needs dino=")
+    if dino_grad and dino_out is not None:
+        raise ValueError("sharded_patch_step: dino_grad=True together with dino_out= -- a differentiable extractor call owns its outputs")
     rank, world = _world(group)
     own = local_patches(n_patches, rank, world)
     if rays.shape[1] != len(own):
@@ -561,7 +570,10 @@ def sharded_patch_step(net, rays: torch.Tensor, bounds, n_patches: int, feat: Op
             ev_d = torch.cuda.Event(enable_timing=True)
             ev_d.record()
         if len(own):
-            f = dino.patch_features(ret["rgb"].detach(), int(patch_stride), want_attn=False, **({} if dino_out is None else {"out": dino_out}))
+            if dino_grad:
+                f = dino.patch_features(ret["rgb"], int(patch_stride), differentiable=True, want_attn=False)
+            else:
+                f = dino.patch_features(ret["rgb"].detach(), int(patch_stride), want_attn=False, **({} if dino_out is None else {"out": dino_out}))
             feat, cls_tokens = f["feats"], f["cls_tokens"]
         else:   # nothing rendered, nothing extracted: empty slots of the gather's widths (all_gather_patches sizes them by shape[1:])
             feat, cls_tokens = rays.new_zeros((0, 384, 14, 14)), rays.new_zeros((0, 384))

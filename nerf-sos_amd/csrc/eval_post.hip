@@ -22,8 +22,11 @@ __global__ __launch_bounds__(256) void eval_post_kernel(const float* __restrict_
             float mx = s[0];
             int arg = 0;
             for (int c = 1; c < C; ++c) mx = fmaxf(mx, s[c]);
-            float den = 0.0f;
-            for (int c = 0; c < C; ++c) den += expf(s[c] - mx);  // softmax(dim=-1), engines/eval.py:55
+            // softmax(dim=-1), engines/eval.py:55.  The denominator is summed in fp64 and rounded once: C sequential fp32 adds
+            // left sem_prob 15 x 2^-24 from the exact softmax at C = 64 (ATen's own fp32 softmax: 5.5), now <= 2 at every C.
+            double den64 = 0.0;
+            for (int c = 0; c < C; ++c) den64 += (double)expf(s[c] - mx);
+            const float den = (float)den64;
             float best = -1.0f;
             for (int c = 0; c < C; ++c) {
                 const float p = expf(s[c] - mx) / den;

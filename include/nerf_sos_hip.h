@@ -31,12 +31,14 @@ extern "C" {
  * sem_hid16 of the default 16-bit kernel, nsos_mlp_save16_layout's NSOS_SEM_HID_TILED bit; 6: `scale` of nsos_mlp_input_grads_x3[_a16]
  * is three floats -- trunk scale, colour-branch factor, semantic-branch factor; 7: the generic kernels' packed program gained a field
  * (GenOp::ksplit_off: an older binding's buffer sizes still agree, but the two sides must match) + nsos_wgrad_batch; 9: evaluation metrics
- * nsos_ssim, nsos_adjusted_rand, nsos_kmeans; 10: the DINO ViT-S/16 feature extractor nsos_dino_*).  The folded fp32 stream
+ * nsos_ssim, nsos_adjusted_rand, nsos_kmeans; 10: the DINO ViT-S/16 feature extractor nsos_dino_*;
+ * 11: the 16-bit packed weights hold two streams instead of three -- nsos_mlp_packed_bytes_lp -- and nsos_mlp_lp_select_kernel /
+ * NSOS_LP_KERNEL refuse the retired kernel 2).  The folded fp32 stream
  * (nsos_mlp_pack_fold / nsos_mlp_*_fold) only ADDS entry points -- no existing argument list or buffer format moved, so the version
  * stands; a library without them fails to bind (every declared symbol is resolved at load) and reports another source hash.  The same
  * holds for LPIPS (nsos_lpips_*): four new entry points, nothing existing moved -- for the camera layer (nsos_camera_*): three -- and for
  * DINO's backward to the input (nsos_dino_forward_save, nsos_dino_backward and their four size / pack functions). */
-#define NSOS_ABI_VERSION 10
+#define NSOS_ABI_VERSION 11
 
 enum {
     NSOS_OK = 0,
@@ -382,14 +384,17 @@ int32_t nsos_sem_head_wgrad_x3(const float* weights, const float* g_semantics, c
 /* ---- K2-LP: the same fused network with 16-bit MFMA inputs and fp32 accumulation (reduced-precision configs) ----
  * For BASELINE configs C3 (bf16) and C5 (fp16, eval-only).  NOT bit/1e-4-comparable with the reference's fp32
  * arithmetic (fp16: ~1e-3 relative, bf16: ~1e-2); never used by the fp32 parity path.  Weights are packed to 16
- * bit by nsos_mlp_pack_lp into their own stream layout (nsos_mlp_packed_bytes_lp bytes).  raw out is fp32. */
+ * bit by nsos_mlp_pack_lp into their own layout (nsos_mlp_packed_bytes_lp bytes): [the vector-ALU heads' block, 4 KiB | the
+ * stream of mlp_lp_kernel, 37 / 39 / 40 chunks of 36 KiB for sem_mode 0 / 1 / 2 | the stream of mlp_lp16_kernel, 37 / 39 / 39
+ * chunks of 36 KiB + 4 KiB].  raw out is fp32. */
 enum { NSOS_DTYPE_F32 = 0, NSOS_DTYPE_F16 = 1, NSOS_DTYPE_BF16 = 2 };
 size_t nsos_mlp_packed_bytes_lp(int32_t sem_mode);
 int32_t nsos_mlp_pack_lp(const nsos_mlp_tensors* tensors, int32_t sem_mode, int32_t dtype, void* packed,
                          size_t packed_bytes, void* stream);
-/* Re-pack only what depends on semantic_linear.* (the head's chunks of every stream + the vector-ALU heads' block) into a buffer
- * that already holds a full nsos_mlp_pack_lp of the same trunk: the shipped recipe trains the semantic heads alone
- * (run_nerf.py:307-318), so a training step re-packs 3 chunks per stream instead of 37-40.  sem_mode PLAIN / COORD only. */
+/* Re-pack only what depends on semantic_linear.* (the head's chunks of the SELECTED kernel's stream, with the vector-ALU heads'
+ * block where that kernel reads it) into a buffer that already holds a full nsos_mlp_pack_lp of the same trunk: the shipped recipe
+ * trains the semantic heads alone (run_nerf.py:307-318), so a training step re-packs 3 chunks instead of 37-40.  The other stream
+ * keeps its old heads: a launch that takes it needs a full pack first.  sem_mode PLAIN / COORD only. */
 int32_t nsos_mlp_pack_lp_heads(const nsos_mlp_tensors* tensors, int32_t sem_mode, int32_t dtype, void* packed,
                                size_t packed_bytes, void* stream);
 int32_t nsos_mlp_forward_rays_lp(const void* packed, int32_t sem_mode, int32_t dtype, const float* rays_o,
@@ -406,7 +411,8 @@ int32_t nsos_mlp_forward_rays_save_lp(const void* packed, int32_t sem_mode, int3
  * rounded to nearest even -- the ReLU pattern is unchanged, the values feed only d semantic_linear.2.weight, at the
  * format's precision like everything else on this path).  896 B per point in all (round 2: 1152).
  * Consumer: nsos_sem_head_wgrad_x3 with the matching sem_in_dtype.
- * LAYOUT of sem_in16 -- nsos_mlp_save16_layout(n_points) says which one the call will write:
+ * LAYOUT -- nsos_mlp_save16_layout(n_points) says what the call will write: NSOS_SEM_IN_ROWS (both matrices row-major: the
+ * round-1 kernel) or NSOS_SEM_IN_TILED | NSOS_SEM_HID_TILED (both tile-major: the default kernel), or a negative NSOS_ERR_*.
  *   NSOS_SEM_IN_ROWS  (0):  [P, 320] row-major;
  *   NSOS_SEM_IN_TILED (16): tile-major, the layout the two-waves-per-SIMD kernel (the default) stores without touching 32
  *     different rows per instruction: groups of 32 consecutive points, [group][K 0..19][kg 0..1][point 0..31][8 channels] --
@@ -516,11 +522,16 @@ int32_t nsos_mlp_profile_rays_fold(const void* packed, int32_t sem_mode, const f
  * nsos_mlp_profile_rays_lp), or stop with NULL.  scripts/phase_profile_lp.py --save. */
 int32_t nsos_mlp_lp_set_stamp_buffer(uint64_t* stamps);
 
-/* Diagnostics: which kernel serves the 16-bit entry points above.  2 (default) = two 256-register waves per SIMD, 32 points
- * each (mlp_lp8.hip); 1 = the round-1 kernel, one 512-register wave per SIMD with 64 points (mlp_lp.hip).  Same packed
- * stream, bit-identical results; exists for A/B measurements (models/nerf_mlp.py:67-100 is what both replace). */
-int32_t nsos_mlp_lp_select_kernel(int32_t waves_per_simd);
-int32_t nsos_mlp_lp_selected_kernel(void);   /* 3 = mlp_lp16_kernel (default), 2 = mlp_lp8_kernel, 1 = mlp_lp_kernel */
+/* Diagnostics: which kernel serves the 16-bit entry points above.  3 (default) = mlp_lp16_kernel, two 256-register waves per
+ * SIMD with 32 points each on 16x16x32 MFMAs (mlp_lp16.hip); 1 = mlp_lp_kernel, the round-1 kernel, one 512-register wave per
+ * SIMD with 64 points on 32x32x16 (mlp_lp.hip).  Each reads its own stream of the packed weights; the two agree to the 16-bit
+ * format's rounding.  Exists for A/B measurements (models/nerf_mlp.py:67-100 is what both replace).  Every other value -- 2, a
+ * retired kernel, included -- is NSOS_ERR_UNSUPPORTED and leaves the selection as it was.  NSOS_LP_KERNEL=lp16|lp4 in the
+ * environment sets the initial selection; with any other value nsos_mlp_lp_selected_kernel and the 16-bit pack, forward, save and
+ * nsos_mlp_save16_layout calls return NSOS_ERR_UNSUPPORTED until a kernel is selected here.
+ * Whatever is selected, the fp32 operands of nsos_mlp_forward_rays_save_lp and launches of 2^31 points or more run on kernel 1. */
+int32_t nsos_mlp_lp_select_kernel(int32_t kernel);
+int32_t nsos_mlp_lp_selected_kernel(void);   /* 3 = mlp_lp16_kernel (default), 1 = mlp_lp_kernel, or NSOS_ERR_UNSUPPORTED */
 
 /* ... and for the split-fp16 kernel (128-point tiles: more than 2 x 128 x (CU count) points).  scripts/phase_profile_x3.py. */
 int32_t nsos_mlp_profile_rays_x3(const void* packed, int32_t sem_mode, const float* rays_o, const float* rays_d,

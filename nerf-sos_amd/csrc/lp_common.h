@@ -1,4 +1,4 @@
-// Shared pieces of the 16-bit MLP kernels (mlp_lp.hip: 4 waves x 64 points; mlp_lp8.hip: 8 waves x 32 points):
+// Shared pieces of the 16-bit MLP kernels (mlp_lp.hip: 4 waves x 64 points on 32x32x16; mlp_lp16.hip: 8 waves x 32 points on 16x16x32):
 // number formats, the accumulator -> packed-B-operand conversion, parameters, encoding slices, VALU heads.
 #pragma once
 #include "mlp_common.h"
@@ -31,13 +31,13 @@ constexpr int kAuxSem2W = 512;    // 2 x 128 fp32
 constexpr int kAuxScalars = 768;  // alpha_b, rgb_b[3], sem2_b[2]
 constexpr int kAuxWords = 1024;
 
-enum ChunkKind { kHid8 = 0, kEnc8 = 1, kHid4 = 2, kEnc4 = 3, kDir4 = 4,
-                 kPair8 = 5 };   // mlp_lp8's tile-pair-major hidden chunk: [bias t0, bias t1, (s0,t0), (s0,t1), (s1,t0), ...], t = 2c + {0,1}
+enum ChunkKind { kHid8 = 0, kEnc8 = 1, kHid4 = 2, kEnc4 = 3, kDir4 = 4 };
 
 __host__ __device__ constexpr int lp_chunks(int sem) {
     // L0 enc(1) + 8 hidden layers x 4 + L5 enc(1) + [sem0 hid(2) (+enc 1)] + views hid(2) + dir(1)
     return 1 + 32 + 1 + (sem ? 2 + (sem == 2 ? 1 : 0) : 0) + 3;
 }
+__host__ __device__ constexpr size_t lp_stream_bytes(int sem) { return (size_t)lp_chunks(sem) * kSlotBytes; }
 
 struct F16 {
     static constexpr bool kIsF16 = true;
@@ -199,7 +199,7 @@ __device__ __forceinline__ void heads_partial_f32(const f32x16 (&h)[NT], const f
         }
 }
 
-// sem_mode x dtype x SAVE of the three 16-bit kernels: f(T{}, SEM, SAVE) with the number-format class and two integral constants.
+// sem_mode x dtype x SAVE of the 16-bit kernels: f(T{}, SEM, SAVE) with the number-format class and two integral constants.
 // The training variants (SAVE) store the semantic head's inputs: there is none for NSOS_SEM_NONE.
 template <class F>
 int32_t dispatch_lp(int32_t sem_mode, int32_t dtype, bool save, F&& f) {
@@ -213,10 +213,8 @@ int32_t dispatch_lp(int32_t sem_mode, int32_t dtype, bool save, F&& f) {
     });
 }
 
-// mlp_lp8.hip: the two-waves-per-SIMD kernel (8 waves x 32 points per 256-point tile), same packed stream and results
-int32_t launch_lp8(const LpParams& p, int32_t sem_mode, int32_t dtype, bool save, hipStream_t stream);
-
-// mlp_lp16.hip: the same workgroup shape on v_mfma_f32_16x16x32 (its own packed stream: p.chunks points at it)
+// mlp_lp16.hip: the two-waves-per-SIMD kernel (8 waves x 32 points per 256-point tile) on v_mfma_f32_16x16x32 (its own packed
+// stream: p.chunks points at it)
 __host__ __device__ constexpr int lp16_chunks(int sem) {
     // L0 (1) + 7 quad layers x 4 + L5 h (4) + L5 x63 (1) + [sem0 h (2) + tail (1) | sigma (1)] + views (2)
     return 1 + 28 + 5 + (sem ? 3 : 1) + 2;

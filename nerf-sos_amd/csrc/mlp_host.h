@@ -1,4 +1,4 @@
-// Host side of the persistent MLP kernel families (mlp_fused, mlp_lp, mlp_lp8, mlp_lp16, mlp_x3, mlp_x316, mlp_x3_bwd): the
+// Host side of the persistent MLP kernel families (mlp_fused, mlp_lp, mlp_lp16, mlp_x3, mlp_x316, mlp_x3_bwd): the
 // argument checks, the parameter fill, the sem_mode / dtype dispatch and the launch they all share.  No device code.
 // The ORDER of the checks is part of the C ABI (a call that is wrong in two ways reports the first): every family refuses in
 //   NULL pointer -> shape -> [n_rays bound] -> [mode] -> alignment -> tile count,

@@ -18,6 +18,7 @@
 //   * sigma head: v_dot2c on the packed activations; rgb / semantics heads: fp32 VALU on the fp32 accumulators.
 // Compiled with -ffp-contract=off (x = o + d*z stays a separately rounded multiply and add).
 #include <cstdlib>
+#include <cstring>
 
 #include "lp_common.h"
 
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(256, 1) void mlp_lp_kernel(const LpParams P) {
             if (l == 7) {
                 // sigma head: dot of the packed activations with packed weights (models/nerf_mlp.py:77)
                 const unsigned* aw = aux_l + kAuxAlphaW + kg * 64;
-                // four chains per column (one per packed word q), then (p0 + p1) + (p2 + p3): the order mlp_lp8_kernel sums in
+                // four chains per column (one per packed word q), then (p0 + p1) + (p2 + p3): four short chains instead of one of 64 dependent v_dot2c
                 float pq[2][4];
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
@@ -411,14 +412,7 @@ __global__ __launch_bounds__(256) void lp_pack_kernel(const LpPackParams P) {
     const int g = within >> 9, lane = (within >> 3) & 63, e = within & 7;  // 512 elements per A operand
     const int i = lane & 31, kgl = lane >> 5, m = 8 * kgl + e;
     float v = 0.0f;
-    if (g < ck.n_groups && ck.kind == kPair8) {   // a0 = tile pair c: operands [bias 2c, bias 2c+1, then slice-major over the two tiles]
-        const int t = 2 * ck.a0 + (g < 2 ? g : ((g - 2) & 1));
-        if (g < 2) v = (m == 0) ? ck.bias[32 * t + i] : 0.0f;
-        else {
-            const int s = (g - 2) >> 1;
-            v = ck.w[(long long)(32 * t + i) * ck.in_dim + ck.col_base + acc_feature(s >> 1, 8 * (s & 1) + e, kgl)];
-        }
-    } else if (g < ck.n_groups) {
+    if (g < ck.n_groups) {
         const int a = ck.a0 + g;
         const bool eight = ck.kind == kHid8 || ck.kind == kEnc8;
         const int nt = eight ? 8 : 4;
@@ -453,22 +447,35 @@ int32_t launch_lp(const LpParams& p, hipStream_t stream) {
 // ------------------------------------------------------------------------------------------ C ABI
 extern "C" size_t nsos_mlp_packed_bytes_lp(int32_t sem_mode) {
     if (sem_mode < 0 || sem_mode > 2) return 0;
-    // aux + the slice-major stream of mlp_lp_kernel + the stream of mlp_lp8_kernel (tile-pair-major hidden layers) + the stream
-    // of mlp_lp16_kernel (16x16x32 tiles, tile-quad-major hidden layers)
-    return (size_t)kAuxWords * 4 + 2 * (size_t)lp_chunks(sem_mode) * kSlotBytes + lp16_stream_bytes(sem_mode);
+    // aux + the slice-major stream of mlp_lp_kernel + the stream of mlp_lp16_kernel (16x16x32 tiles, tile-quad-major hidden layers)
+    return (size_t)kAuxWords * 4 + lp_stream_bytes(sem_mode) + lp16_stream_bytes(sem_mode);
+}
+
+// which kernel serves the 16-bit path: 3 = mlp_lp16_kernel (two waves per SIMD on v_mfma_f32_16x16x32; default), 1 = mlp_lp_kernel
+// (round 1: one 512-register wave per SIMD, 64 points, 32x32x16).  NSOS_LP_KERNEL=lp16|lp4 in the environment or
+// nsos_mlp_lp_select_kernel(3|1) select one for A/B measurements; lp16 agrees with lp4 to the 16-bit formats' rounding (other
+// contraction order, 16-bit heads: mlp_lp16.hip).  (2 was the 32x32x16 two-waves-per-SIMD kernel of rounds 2-3, retired: the value
+// is refused, not reused.)  Any other NSOS_LP_KERNEL is NSOS_ERR_UNSUPPORTED here and in every entry that asks, rather than a run
+// of the default under another kernel's name.
+static int g_lp_selected_kernel = 0;
+static int lp_selected_kernel() {
+    if (g_lp_selected_kernel == 0) {
+        const char* k = getenv("NSOS_LP_KERNEL");
+        g_lp_selected_kernel = !k || !strcmp(k, "lp16") ? 3 : (!strcmp(k, "lp4") ? 1 : NSOS_ERR_UNSUPPORTED);
+    }
+    return g_lp_selected_kernel;
 }
 
 static int32_t pack_lp_impl(const nsos_mlp_tensors* T_, int32_t sem_mode, int32_t dtype, void* packed, size_t packed_bytes, void* stream,
                             bool heads_only);
-static int lp_waves_per_simd();
 extern "C" int32_t nsos_mlp_pack_lp(const nsos_mlp_tensors* T_, int32_t sem_mode, int32_t dtype, void* packed,
                                     size_t packed_bytes, void* stream) {
     return pack_lp_impl(T_, sem_mode, dtype, packed, packed_bytes, stream, false);
 }
-// Only what depends on semantic_linear.*: the head's chunks of all three streams (chunks 30.. of each: the trunk's 30 chunks come
-// first in every layout) and the aux block.  For the shipped training recipe (--fix_backbone: only the semantic heads train,
-// run_nerf.py:307-318) a step re-packs 3 chunks instead of 37-40 -- and only in the stream of the kernel that is selected NOW
-// (nsos_mlp_lp_selected_kernel: one launch per net and step instead of three); `packed` must hold a full pack of the same trunk.
+// Only what depends on semantic_linear.*: the head's chunks (chunks 30.. of a stream: the trunk's 30 chunks come first in both
+// layouts) and, for mlp_lp_kernel, the aux block (mlp_lp16_kernel does not read it).  For the shipped training recipe
+// (--fix_backbone: only the semantic heads train, run_nerf.py:307-318) a step re-packs 3 chunks instead of 37-40 -- and only in the stream of the kernel that is selected NOW
+// (nsos_mlp_lp_selected_kernel: one launch per net and step instead of two); `packed` must hold a full pack of the same trunk.
 // CONTRACT: after a heads-only re-pack only the selected kernel's stream is current.  A launch that takes another stream -- after
 // nsos_mlp_lp_select_kernel, or forward_rays_lp's fall-back to the round-1 kernel on stream 0 (fp32 sem_in saves:
 // nsos_mlp_forward_rays_save_lp; launches of >= 2^31 points) -- needs a FULL pack first.  The Python layer enforces it: ops.PackPlan
@@ -485,34 +492,35 @@ static int32_t pack_lp_impl(const nsos_mlp_tensors* T_, int32_t sem_mode, int32_
                                        nsos_mlp_packed_bytes_lp(sem_mode));
     if (ok != NSOS_OK) return ok;
 
-    const int X = NSOS_XYZ_DIM, W = NSOS_NET_WIDTH;
-    const int selected = lp_waves_per_simd();
-    for (int layout = 0; layout < 2; ++layout) {   // 0: slice-major hidden layers (mlp_lp_kernel), 1: tile-pair-major (mlp_lp8_kernel)
-        if (heads_only && selected != layout + 1) continue;
+    const int selected = lp_selected_kernel();
+    NSOS_REQUIRE(selected > 0, selected);
+    unsigned* const aux = static_cast<unsigned*>(packed);
+    unsigned char* const stream4 = reinterpret_cast<unsigned char*>(aux + kAuxWords);
+    if (!heads_only || selected == 1) {   // aux + the slice-major stream of mlp_lp_kernel
+        const int X = NSOS_XYZ_DIM, W = NSOS_NET_WIDTH;
         LpPackParams P = {};
         int n = 0;
         auto add = [&](const float* w, const float* bias, int in_dim, int col, int kind, int a0, int ng) {
             P.ch[n++] = LpChunk{w, bias, in_dim, col, kind, a0, ng};
         };
-        auto hidden8 = [&](const float* w, const float* b, int in_dim, int col, bool pairs) {
-            for (int c = 0; c < 4; ++c) pairs ? add(w, b, in_dim, col, kPair8, c, 34) : add(w, b, in_dim, col, kHid8, 34 * c, 34);
+        auto hidden8 = [&](const float* w, const float* b, int in_dim, int col) {
+            for (int c = 0; c < 4; ++c) add(w, b, in_dim, col, kHid8, 34 * c, 34);
         };
         auto hidden4 = [&](const float* w, const float* b, int in_dim, int col) {
             for (int c = 0; c < 2; ++c) add(w, b, in_dim, col, kHid4, 34 * c, 34);
         };
-        const bool pm = layout == 1;
         add(T_->pts_w[0], T_->pts_b[0], X, 0, kEnc8, 0, 32);  // bias in the pad slot
-        for (int l = 1; l <= 4; ++l) hidden8(T_->pts_w[l], T_->pts_b[l], W, 0, pm);
-        hidden8(T_->pts_w[5], T_->pts_b[5], X + W, X, false);  // skip layer: h part (with its bias slice), slice-major in both ...
+        for (int l = 1; l <= 4; ++l) hidden8(T_->pts_w[l], T_->pts_b[l], W, 0);
+        hidden8(T_->pts_w[5], T_->pts_b[5], X + W, X);         // skip layer: h part (with its bias slice) ...
         add(T_->pts_w[5], nullptr, X + W, 0, kEnc8, 0, 32);    // ... then the x63 part
-        hidden8(T_->pts_w[6], T_->pts_b[6], W, 0, pm);
-        hidden8(T_->pts_w[7], T_->pts_b[7], W, 0, pm);
+        hidden8(T_->pts_w[6], T_->pts_b[6], W, 0);
+        hidden8(T_->pts_w[7], T_->pts_b[7], W, 0);
         if (sem_mode) {
             const int in_dim = sem_mode == NSOS_SEM_COORD ? W + X : W;
             hidden4(T_->sem0_w, T_->sem0_b, in_dim, 0);
             if (sem_mode == NSOS_SEM_COORD) add(T_->sem0_w, nullptr, in_dim, W, kEnc4, 0, 16);
         }
-        hidden8(T_->feature_w, T_->feature_b, W, 0, pm);
+        hidden8(T_->feature_w, T_->feature_b, W, 0);
         hidden4(T_->views_w, T_->views_b, W + NSOS_DIR_DIM, 0);
         add(T_->views_w, nullptr, W + NSOS_DIR_DIM, W, kDir4, 0, 8);
         NSOS_REQUIRE(n == lp_chunks(sem_mode), NSOS_ERR_UNSUPPORTED);
@@ -523,35 +531,17 @@ static int32_t pack_lp_impl(const nsos_mlp_tensors* T_, int32_t sem_mode, int32_
         P.rgb_w = T_->rgb_w; P.rgb_b = T_->rgb_b;
         P.sem2_w = sem_mode ? T_->sem2_w : nullptr;
         P.sem2_b = sem_mode ? T_->sem2_b : nullptr;
-        P.aux = static_cast<unsigned*>(packed);
-        P.chunks = reinterpret_cast<unsigned short*>(P.aux + kAuxWords) + (size_t)layout * n * (kSlotBytes / 2);
+        P.aux = aux;
+        P.chunks = reinterpret_cast<unsigned short*>(stream4);
         const long long total = (long long)P.count * (kSlotBytes / 2);
         const dim3 grid((unsigned)((total + 255) / 256)), block(256);
         if (dtype == NSOS_DTYPE_F16) hipLaunchKernelGGL(lp_pack_kernel<F16>, grid, block, 0, (hipStream_t)stream, P);
         else hipLaunchKernelGGL(lp_pack_kernel<BF16>, grid, block, 0, (hipStream_t)stream, P);
+        const int32_t rc = nsos_launch_status();
+        if (rc != NSOS_OK) return rc;
     }
-    const int32_t rc = nsos_launch_status();
-    if (rc != NSOS_OK) return rc;
-    unsigned char* stream16 = reinterpret_cast<unsigned char*>(static_cast<unsigned*>(packed) + kAuxWords) + 2 * (size_t)lp_chunks(sem_mode) * kSlotBytes;
     if (heads_only && selected != 3) return NSOS_OK;
-    return pack_lp16(T_, sem_mode, dtype == NSOS_DTYPE_F16, stream16, (hipStream_t)stream, heads_only);
-}
-
-// which kernel serves the 16-bit path: 3 = mlp_lp16_kernel (round 4: two waves per SIMD on v_mfma_f32_16x16x32; default),
-// 2 = mlp_lp8_kernel (rounds 2-3: two 256-register waves per SIMD on 32x32x16), 1 = mlp_lp_kernel (round 1: one 512-register
-// wave per SIMD, 64 points).  NSOS_LP_KERNEL=lp16|lp8|lp4 (or the older NSOS_LP_WAVES=4) in the environment or
-// nsos_mlp_lp_select_kernel(3|2|1) select one for A/B measurements; lp8 and lp4 are bit-identical to each other, lp16 agrees
-// with them to the 16-bit formats' rounding (other contraction order, 16-bit heads: mlp_lp16.hip).
-static int g_lp_waves_per_simd = 0;
-static int lp_waves_per_simd() {
-    if (g_lp_waves_per_simd == 0) {
-        const char* e = getenv("NSOS_LP_WAVES");
-        const char* k = getenv("NSOS_LP_KERNEL");
-        g_lp_waves_per_simd = 3;
-        if (e && e[0] == '4') g_lp_waves_per_simd = 1;
-        if (k && k[0] == 'l' && k[1] == 'p') g_lp_waves_per_simd = k[2] == '4' ? 1 : (k[2] == '8' ? 2 : 3);
-    }
-    return g_lp_waves_per_simd;
+    return pack_lp16(T_, sem_mode, dtype == NSOS_DTYPE_F16, stream4 + lp_stream_bytes(sem_mode), (hipStream_t)stream, heads_only);
 }
 
 // diagnostics: a stamp buffer for EVERY following 16-bit launch (inference and training variants alike), or NULL to stop;
@@ -562,13 +552,18 @@ extern "C" int32_t nsos_mlp_lp_set_stamp_buffer(uint64_t* stamps) {
     return NSOS_OK;
 }
 
-extern "C" int32_t nsos_mlp_lp_selected_kernel(void) { return lp_waves_per_simd(); }
+extern "C" int32_t nsos_mlp_lp_selected_kernel(void) { return lp_selected_kernel(); }
 
-extern "C" int32_t nsos_mlp_lp_select_kernel(int32_t waves_per_simd) {
-    NSOS_REQUIRE(waves_per_simd >= 1 && waves_per_simd <= 3, NSOS_ERR_UNSUPPORTED);
-    g_lp_waves_per_simd = waves_per_simd;
+extern "C" int32_t nsos_mlp_lp_select_kernel(int32_t kernel) {
+    NSOS_REQUIRE(kernel == 1 || kernel == 3, NSOS_ERR_UNSUPPORTED);
+    g_lp_selected_kernel = kernel;
     return NSOS_OK;
 }
+
+// the default kernel indexes its points with 32 bits and its training variant stores the compact 16-bit operands only: launches of
+// 2^31 points or more (11 M rays x 192 samples) and the fp32 sem_in / sem_hid of nsos_mlp_forward_rays_save_lp (tests and the
+// exact-kernel backward) take the round-1 kernel whatever is selected
+static bool runs_lp16(int selected, long long n_pts) { return selected == 3 && n_pts < (1ll << 31); }
 
 static int32_t forward_rays_lp(const NsosRayCall& c, int32_t sem_mode, int32_t dtype, unsigned long long* prof, float* sem_in,
                                float* sem_hid, void* stream, unsigned* sem_in16 = nullptr, unsigned* sem_hid16 = nullptr) {
@@ -587,18 +582,11 @@ static int32_t forward_rays_lp(const NsosRayCall& c, int32_t sem_mode, int32_t d
     const hipStream_t st = (hipStream_t)stream;
     const bool save = sem_in || sem_in16;   // the training variants need a semantic head and the matching second output
     if (save) NSOS_REQUIRE((sem_in16 ? (void*)sem_hid16 : (void*)sem_hid) && sem_mode != NSOS_SEM_NONE, NSOS_ERR_UNSUPPORTED);
-    // NSOS_LP_WAVES=4 selects the one-wave-per-SIMD kernel of round 1 (A/B measurements); default: two waves per SIMD
-    // (mlp_lp8_kernel indexes its points with 32 bits: launches of 2^31 points or more -- 11 M rays x 192 samples -- take the
-    //  round-1 kernel, whose results are bit-identical)
-    // (its training variant stores the compact 16-bit operands only: the fp32 sem_in / sem_hid of nsos_mlp_forward_rays_save_lp
-    //  -- tests and the exact-kernel backward -- come from the round-1 kernel as well)
-    if (lp_waves_per_simd() >= 2 && p.n_pts < (1ll << 31) && !(sem_in && !sem_in16)) {
-        if (lp_waves_per_simd() == 3) {
-            p.chunks += 2 * (size_t)lp_chunks(sem_mode) * kSlotBytes;   // the third stream: 16x16x32 tiles
-            return launch_lp16(p, sem_mode, dtype, save, st);
-        }
-        p.chunks += (size_t)lp_chunks(sem_mode) * kSlotBytes;   // the second stream: tile-pair-major hidden layers
-        return launch_lp8(p, sem_mode, dtype, save, st);
+    const int selected = lp_selected_kernel();
+    NSOS_REQUIRE(selected > 0, selected);
+    if (runs_lp16(selected, p.n_pts) && !(sem_in && !sem_in16)) {
+        p.chunks += lp_stream_bytes(sem_mode);   // the second stream: 16x16x32 tiles
+        return launch_lp16(p, sem_mode, dtype, save, st);
     }
     return dispatch_lp(sem_mode, dtype, save, [&](auto t, auto sem, auto sv) -> int32_t {
         return launch_lp<decltype(t), decltype(sem)::value, decltype(sv)::value != 0>(p, st);
@@ -624,8 +612,9 @@ extern "C" int32_t nsos_mlp_forward_rays_save_lp(const void* packed, int32_t sem
 }
 
 extern "C" int32_t nsos_mlp_save16_layout(int64_t n_points) {   // the same condition forward_rays_lp selects the kernel by
-    if (!(lp_waves_per_simd() >= 2 && n_points < (1ll << 31))) return NSOS_SEM_IN_ROWS;
-    return lp_waves_per_simd() == 3 ? (NSOS_SEM_IN_TILED | NSOS_SEM_HID_TILED) : NSOS_SEM_IN_TILED;
+    const int selected = lp_selected_kernel();
+    NSOS_REQUIRE(selected > 0, selected);
+    return runs_lp16(selected, n_points) ? (NSOS_SEM_IN_TILED | NSOS_SEM_HID_TILED) : NSOS_SEM_IN_ROWS;
 }
 
 extern "C" int32_t nsos_mlp_forward_rays_save16_lp(const void* packed, int32_t sem_mode, int32_t dtype, const float* rays_o,

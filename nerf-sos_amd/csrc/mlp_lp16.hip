@@ -1,8 +1,9 @@
 // K2-LP16: the 16-bit fused positional-encoding + MLP kernel on v_mfma_f32_16x16x32 (round 4; the default 16-bit kernel).
-// Same network and the same replaced reference code as mlp_lp.hip / mlp_lp8.hip (models/embedder.py:34-48,
-// models/nerf_mlp.py:67-100,179-215), same workgroup shape as mlp_lp8_kernel (8 waves = two per SIMD, <= 256 registers,
-// 32 points per wave, 256-point tiles, four 36 KiB weight slots fed by global->LDS DMA, one barrier per chunk, the
-// continuous 4-deep A-operand ring) -- re-tiled for the OTHER 16-bit MFMA shape.
+// Same network and the same replaced reference code as mlp_lp.hip (models/embedder.py:34-48,
+// models/nerf_mlp.py:67-100,179-215).  Workgroup shape: 8 waves = two per SIMD, <= 256 registers, 32 points per wave,
+// 256-point tiles, four 36 KiB weight slots fed by global->LDS DMA, one barrier per chunk, the continuous 4-deep A-operand
+// ring.  That shape comes from this kernel's predecessor on v_mfma_f32_32x32x16 (rounds 2-3, retired: DESIGN.md section 4
+// says where its record lives); this kernel re-tiled it for the OTHER 16-bit MFMA shape.
 //
 // Why.  The chip runs this kernel against its power limit, and what the matrix pipe sustains there depends on the MFMA
 // shape: scripts/ubench/mfma_mix.hip (profiles/r04/a_mfma_mix.txt), network-like operands, two waves per SIMD, pipe 98 %
@@ -10,7 +11,7 @@
 //     v_mfma_f32_32x32x16_bf16  operands in registers 1805 TF (1.75 GHz)   A operand through LDS 1626 TF (1.58 GHz)
 //     v_mfma_f32_16x16x32_bf16                         2150 TF (2.09 GHz)                         1878 TF (1.84 GHz)
 // i.e. +15-19 % at equal occupancy (per 32 kFLOP the 32x32 shape moves A 4 + B 4 + C 16 + D 16 register vectors, the 16x16
-// shape 2 x (B 4 + C 4 + D 4) + A 4).  Three rounds of removing cycles from mlp_lp8_kernel had returned about half of
+// shape 2 x (B 4 + C 4 + D 4) + A 4).  Three rounds of removing cycles from the 32x32x16 predecessor had returned about half of
 // every saving as a lower clock; this changes what a cycle costs.
 //
 // Shape.  lane = 16 q + n.  A wave's 32 points are two COLUMN BLOCKS c of 16 points (point 16 c + n); every lane works
@@ -19,12 +20,12 @@
 // (n, q) holds features 16 t + 4 q + r of point 16 c + n.  A K-SLICE is 32 input features = two tiles: the B operand of
 // slice s for block c is H[s][c] = pack16(Z[2s][c][0..3], Z[2s+1][c][0..3]) -- the accumulator layout IS the operand
 // layout (k position (q, e) of slice s carries feature 32 s + 16 (e >> 2) + 4 q + (e & 3); the weight stream is packed in
-// that order), so activations never leave the lane: v_cvt_pk + v_pk_max_i16 per packed word, as in mlp_lp8_kernel.
+// that order), so activations never leave the lane: v_cvt_pk + v_pk_max_i16 per packed word.
 // One 1 KiB A operand (16 rows x 32 k) feeds TWO MFMAs (the two column blocks): one ds_read_b128 per 32 kFLOP and wave =
 // 128 B/clk/CU, as before.  Register budget as before: 16 tiles x 2 blocks x 4 = 128 accumulator registers per 256-wide
 // layer, 8 slices x 2 blocks x 4 = 64 for H.
 //
-// What else changed against mlp_lp8_kernel:
+// What else changed against the 32x32x16 predecessor:
 //   * NO bias MFMAs.  There a bias was an A operand multiplied by a B of ones: 2 of a chunk's 34 MFMAs (5.9 % of the matrix
 //     pipe's time; with 16-row tiles it would be 11 %).  Here a hidden layer's chunk carries its four tiles' biases as a 256-byte
 //     block behind its 32 A operands (lane (n, q) of tile t: the four fp32 values bias[16 t + 4 q + r]); the PREVIOUS chunk
@@ -36,8 +37,8 @@
 //     re-loaded one group late).  Layers with an encoding input (0, 5, sem+coord head, view branch) carry the bias in the
 //     encoding's pad column (input 1.0) instead.
 //   * Hidden layers are tile-QUAD-major (chunk c = output tiles 4c..4c+3 over all 8 slices: 32 A operands + the bias block,
-//     64 MFMAs), with the previous quad's activation riding behind the MFMAs exactly as the tile
-//     pairs did (same register counts: a quad buffer is 32 registers, a quad's activation 16 packed words).
+//     64 MFMAs), with the previous quad's activation riding behind the MFMAs exactly as the
+//     predecessor's tile pairs did (same register counts: a quad buffer is 32 registers, a quad's activation 16 packed words).
 //   * The sigma, rgb and semantic-logit heads are MFMAs into ONE 16-row "raw" tile R[c] (rows 0..2 rgb, 3 sigma, 4..5
 //     semantics): 8 + 4 + 4 A operands, 32 MFMAs per wave and tile instead of ~5 k cycles of v_dot2c / fp32 FMA chains on
 //     the vector ALU.  rgb and semantics therefore see the hidden activations and their weights rounded to 16 bits (the
@@ -49,8 +50,8 @@
 //     the pending activations in scratch across the tile boundary: +15 % cycles, profiles/r04).
 //   * The encodings are evaluated for the lane's 2 x 16 feature slots from a per-(q, slot) table in LDS (octave scale per
 //     coordinate + phase: sin(2 pi (frac + 1/4)) = cos), the same two-term revolution arithmetic as Enc::evaluate_hw.
-// Results are NOT bit-identical to mlp_lp_kernel / mlp_lp8_kernel (other contraction order inside the MFMAs, 16-bit heads):
-// tests/test_gpu_parity.py holds all three to the same emulation.
+// Results are NOT bit-identical to mlp_lp_kernel (other contraction order inside the MFMAs, 16-bit heads):
+// tests/test_gpu_parity.py holds both to the same emulation.
 #include "lp_common.h"
 #include "lp16_sched.h"
 
@@ -225,7 +226,9 @@ __global__ __launch_bounds__(64 * kW16, 1) void mlp_lp16_kernel(const LpParams P
     if constexpr (PROF)
         if (P.prof && blockIdx.x < 2 && lane0 == 0 && wave_s < 8) P.prof[(blockIdx.x * 8 + wave_s) * kProfSlots + kProfSlots - 2] = __builtin_readcyclecounter();
     for (int tile = blockIdx.x; tile < P.n_tiles; tile += gridDim.x) {
-        // (lane-dependent loop invariants are re-derived per tile instead of living -- in scratch -- across every chunk: see mlp_lp8.hip)
+        // Lane-dependent constants of the tile body (half-wave selects, point offsets, stage addresses) are loop invariants: LICM
+        // hoists them, they then live across every MFMA chunk of the tile and end up in scratch.  The lane id is laundered once
+        // per tile, so they are re-derived (a handful of VALU) instead of kept.
         int lane = lane0;
         asm volatile("" : "+v"(lane));
         const int n = lane & 15, q = lane >> 4;
@@ -256,8 +259,8 @@ __global__ __launch_bounds__(64 * kW16, 1) void mlp_lp16_kernel(const LpParams P
             asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 nt\n\ts_nop 1" : : "v"(off), "v"(v), "s"(b), "i"(BOFF & 4095) : "memory");   // (s_nop: see the hidden-activation stores)
         };
         if constexpr (SAVE) {
-            // TILE-MAJOR sem_in (include/nerf_sos_hip.h): [group of 32 points][octet 0..39][point][8 channels] -- store K, half kg of
-            // mlp_lp8_kernel is octet 2K + kg.  Lane (n, q) ends up (after one v_permlane16_swap per word pair) with octet
+            // TILE-MAJOR sem_in (include/nerf_sos_hip.h): [group of 32 points][octet 0..39][point][8 channels] -- an octet is
+            // eight consecutive channels of the row.  Lane (n, q) ends up (after one v_permlane16_swap per word pair) with octet
             // 4 s + 2 (q & 1) + (q >> 1) of slice s of relu(h7), and holds octet 32 + 4 s + q of the encoding slice s as it is.
             save_grp = reinterpret_cast<unsigned long long>(P.sem_in16 + (long long)(wave_first >> 5) * 5120);
             save_off = (unsigned)((2 * (q & 1) + (q >> 1)) * 512 + n * 16);
@@ -333,8 +336,10 @@ __global__ __launch_bounds__(64 * kW16, 1) void mlp_lp16_kernel(const LpParams P
                 }
                 ride(ic);
             }, mid, tail, side, nfill);
+            // pin the accumulators here: without a use at the chunk's end LLVM sinks whole chunks of MFMAs below later branches and
+            // keeps their A operands (pending ring registers!) alive in scratch
 #pragma unroll
-            for (int t = 0; t < NT; ++t) asm volatile("" : "+v"(acc[t][0]), "+v"(acc[t][1]));   // (keeps LLVM from sinking the chunk: see mlp_lp8.hip)
+            for (int t = 0; t < NT; ++t) asm volatile("" : "+v"(acc[t][0]), "+v"(acc[t][1]));
         };
         // tile-quad chunk of a hidden layer: 32 A operands, group g = (slice g >> 2, tile g & 3); zq[t][0] holds the tile's bias when the
         // chunk starts (read from LDS by the PREVIOUS chunk -- bias_next below -- or by bias_now): the C operand of both first MFMAs.
@@ -373,7 +378,10 @@ __global__ __launch_bounds__(64 * kW16, 1) void mlp_lp16_kernel(const LpParams P
 
         stamp();  // 1: inputs + xyz encoding
         f32x4 Zq[2][4][2];
-        auto dead = [&]() {   // (see mlp_lp8.hip: the quad buffers are redefined where they are dead)
+        // A value that is only CONDITIONALLY read at the top of a run of quad layers is live, for the compiler, from its last
+        // definition -- through layers 0 and 5, whose 128 accumulators leave no room for 32 more registers.  An empty asm
+        // "defines" the quad buffers afresh where they are dead, at no cost.
+        auto dead = [&]() {
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -533,7 +541,10 @@ __global__ __launch_bounds__(64 * kW16, 1) void mlp_lp16_kernel(const LpParams P
                     u32x4 Sp[4][2];
                     auto from_Hlo = [&](auto sc, auto cc) { return H[decltype(sc)::value][decltype(cc)::value]; };
                     auto from_Hhi = [&](auto sc, auto cc) { return H[4 + decltype(sc)::value][decltype(cc)::value]; };
-                    // SAVE: the first eight stores of relu(h7) ride here (at most three per chunk, six groups apart: see mlp_lp8.hip)
+                    // SAVE: the first eight stores of relu(h7) ride here, EARLY in their chunks, at most three per chunk and six groups
+                    // apart.  The next chunk's barrier waits for every outstanding vector-memory operation (its DMA pieces share the
+                    // counter with the stores): a store issued just ahead of it exposes its whole HBM latency, and a CU's store
+                    // path takes 64 B per clock, so stores bunched behind ONE barrier made that barrier wait for all of them.
                     auto ride_sem = [&](auto gc_, auto ch_c) {
                         constexpr int g = decltype(gc_)::value, CH = decltype(ch_c)::value;
                         if constexpr (SAVE && g >= 3 && (g - 3) % 6 == 0 && (g - 3) / 6 < (CH == 2 ? 2 : 3)) store_h7_k(IC(3 * CH + (g - 3) / 6));
@@ -736,7 +747,10 @@ __global__ __launch_bounds__(64 * kW16, 1) void mlp_lp16_kernel(const LpParams P
                 for (int c = 0; c < 2; ++c)
                     if (q == 0 && 16 * c + n < n_here) *reinterpret_cast<f32x4*>(P.raw + (long long)(wave_first + 16 * c + n) * 4) = R[c];
             } else {
-                // 24 B per point: staged through 768 B of LDS per wave, then 48 lanes store 16 B each (full sectors: see mlp_lp8.hip)
+                // 24 B per point.  Written per lane (8 B pieces) every store instruction covered a third of each 32-byte sector it
+                // touched, and the memory-side write counter showed 2.9x the bytes (partial-line writes).  The wave's 32 points are
+                // 768 contiguous bytes: staged through 768 B of LDS per wave, then 48 lanes store 16 B each -- full sectors, one
+                // store instruction.
                 float* const stage = reinterpret_cast<float*>(lds + kSlots * kSlotBytes + kAuxWords * 4) + wave_s * 192;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");    // the parked ray indices were read above
                 __builtin_amdgcn_wave_barrier();

@@ -283,7 +283,7 @@ __global__ __launch_bounds__(64 * kW16, 1) void mlp_x316_kernel(const X316Params
                 ride(ic);
             }, mid, tail, side, nfill);
 #pragma unroll
-            for (int t = 0; t < NT; ++t) asm volatile("" : "+v"(acc[t][0]), "+v"(acc[t][1]));   // (keeps LLVM from sinking the chunk: see mlp_lp8.hip)
+            for (int t = 0; t < NT; ++t) asm volatile("" : "+v"(acc[t][0]), "+v"(acc[t][1]));   // (keeps LLVM from sinking the chunk below later branches: see slice_chunk in mlp_lp16.hip)
         };
         auto slice_chunk = [&](auto nt_c, auto nsl_c, auto zf_c, auto& acc, auto&& bh, auto&& bl, const int nfill) {
             slice_chunk_r(nt_c, nsl_c, zf_c, acc, bh, bl, [](auto) {}, nfill);
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(64 * kW16, 1) void mlp_x316_kernel(const X316Params
 
         stamp();  // 1: inputs + xyz encoding
         f32x4 Zq[2][2][2];
-        auto dead = [&]() {   // (the pair buffers are redefined where they are dead: see mlp_lp8.hip)
+        auto dead = [&]() {   // (the pair buffers are redefined where they are dead, so that they are not live through layers 0 and 5: see dead() in mlp_lp16.hip)
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll

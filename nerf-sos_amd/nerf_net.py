@@ -218,7 +218,8 @@ class NeRFMLP(nn.Module):
         key = None if trainable else tuple((p.data_ptr(), p._version) for p in params)
         if trainable or precision not in self._packed or key != self._packed_key.get(precision):
             # the shipped recipe trains the semantic heads alone (run_nerf.py:307-318): with the 16-bit streams, re-pack only their
-            # chunks while the frozen trunk's (data_ptr, _version) keys stand (3 chunks per stream instead of 37-40 per step and net)
+            # chunks while the frozen trunk's (data_ptr, _version) keys stand (3 chunks of one stream instead of two streams of 37-40
+            # per step and net)
             heads_only = False
             if trainable and precision in ("fp16", "bf16") and self.sem_mode != ops.SEM_NONE:
                 # (+ the kernel selection: a heads-only re-pack touches the selected kernel's stream only)

@@ -185,7 +185,8 @@ class PackPlan:
 
     def run(self, out: Optional[torch.Tensor] = None, precision: str = "fp32", heads_only: bool = False) -> torch.Tensor:
         """Pack into `out` (allocated if None / too small).  heads_only (fp16 / bf16 with a semantic head): `out` already holds a
-        full pack of the same trunk -- re-pack only what depends on semantic_linear.* (nsos_mlp_pack_lp_heads)."""
+        full pack of the same trunk -- re-pack only what depends on semantic_linear.* (nsos_mlp_pack_lp_heads), and of the buffer's
+        two streams only the selected kernel's (check_lp_stream)."""
         if precision not in DTYPES:
             raise ValueError(f"precision must be one of {list(DTYPES)}, got {precision!r}")
         nbytes = self.nbytes.get(precision)
@@ -211,7 +212,7 @@ class PackPlan:
         return out
 
 
-# Which of a 16-bit weight buffer's three streams holds current semantic-head weights after a heads-only re-pack, keyed by the
+# Which of a 16-bit weight buffer's two streams holds current semantic-head weights after a heads-only re-pack, keyed by the
 # buffer's STORAGE (device, address): every view, reshape or slice of the buffer shares it, so the tag survives them (a
 # Python attribute on the tensor object did not).  A clone is a new storage with no entry -- a clone of a partially re-packed buffer
 # must be re-packed in full by its owner; the C ABI's own callers hold the same obligation (include/nerf_sos_hip.h, nsos_mlp_pack_lp_heads).
@@ -224,8 +225,8 @@ def _storage_key(t: torch.Tensor) -> tuple:
 
 def check_lp_stream(packed: torch.Tensor, kernel: int) -> None:
     """A 16-bit weight buffer that had a heads-only re-pack (PackPlan.run(heads_only=True)) holds current semantic-head weights in
-    ONE of its three streams.  Called with the kernel a launch is about to run on (1 = mlp_lp_kernel, the fall-back for fp32 sem_in
-    saves and >= 2^31 points; 2 = lp8; 3 = lp16): raises instead of rendering with stale heads."""
+    ONE of its two streams.  Called with the kernel a launch is about to run on (1 = mlp_lp_kernel, also the fall-back for fp32 sem_in
+    saves and >= 2^31 points; 3 = mlp_lp16_kernel): raises instead of rendering with stale heads."""
     cur = _LP_PARTIAL.get(_storage_key(packed))
     if cur is not None and cur != kernel:
         raise RuntimeError(f"nerf_sos_amd: this packed 16-bit weight buffer was last updated by a heads-only re-pack for kernel {cur}; the "
@@ -628,8 +629,16 @@ def mlp_profile_rays(packed: torch.Tensor, sem_mode: int, rays_o: torch.Tensor, 
 
 
 def lp_selected_kernel() -> int:
-    """3 = mlp_lp16_kernel (default), 2 = mlp_lp8_kernel, 1 = mlp_lp_kernel (NSOS_LP_KERNEL / nsos_mlp_lp_select_kernel)."""
-    return int(_lib.lib().nsos_mlp_lp_selected_kernel())
+    """3 = mlp_lp16_kernel (default), 1 = mlp_lp_kernel (NSOS_LP_KERNEL=lp16|lp4 / nsos_mlp_lp_select_kernel).  Raises for any
+    other NSOS_LP_KERNEL: the library refuses it instead of running the default under another kernel's name."""
+    return _value_or_raise(_lib.lib().nsos_mlp_lp_selected_kernel(), "nsos_mlp_lp_selected_kernel")
+
+
+def _value_or_raise(value: int, what: str) -> int:
+    """A C entry that answers with a non-negative value or a negative NSOS_ERR_* code."""
+    if value < 0:
+        _lib.check(value, what)
+    return int(value)
 
 
 def mlp_forward_rays_lp(packed: torch.Tensor, sem_mode: int, precision: str, rays_o: torch.Tensor,
@@ -668,19 +677,18 @@ def mlp_forward_rays_save(packed: torch.Tensor, sem_mode: int, rays_o: torch.Ten
     rays_o, rays_d, viewdirs, z_vals, R, S, dev = _rays(rays_o, rays_d, viewdirs, z_vals)
     raw = torch.empty((R, S, 6), device=dev, dtype=torch.float32)
     compact = compact and precision in ("fp16", "bf16")
-    layout = int(_lib.lib().nsos_mlp_save16_layout(R * S)) if compact else 0
-    if layout & SEM_IN_TILED:
-        # tile-major (what the two-waves-per-SIMD kernel stores contiguously): [group of 32 points][K][kg * 32 + point][8 channels];
-        # sem_head_wgrad recognises it by its four dimensions, sem_in_rows() turns it into [P,320]
-        sem_in = torch.empty(((R * S + 31) // 32, 20, 64, 8), device=dev, dtype=torch.float16 if precision == "fp16" else torch.bfloat16)
+    layout = _value_or_raise(_lib.lib().nsos_mlp_save16_layout(R * S), "nsos_mlp_save16_layout") if compact else 0
+    dt = (torch.float16 if precision == "fp16" else torch.bfloat16) if compact else torch.float32
+    if layout == SEM_IN_TILED | SEM_HID_TILED:
+        # both tile-major (what the default 16-bit kernel stores contiguously): sem_in [group of 32 points][K][kg * 32 + point][8 channels],
+        # sem_hid [group of 32 points][octet 0..15][point][8 channels]; sem_head_wgrad recognises them by their four dimensions,
+        # sem_in_rows() / sem_hid_rows() turn them into [P,320] / [P,128]
+        sem_in = torch.empty(((R * S + 31) // 32, 20, 64, 8), device=dev, dtype=dt)
+        sem_hid = torch.empty(((R * S + 31) // 32, 16, 32, 8), device=dev, dtype=dt)
     else:
-        sem_in = torch.empty((R * S, 320), device=dev,
-                             dtype=(torch.float16 if precision == "fp16" else torch.bfloat16) if compact else torch.float32)
-    if layout & SEM_HID_TILED:
-        # tile-major like sem_in (the default 16-bit kernel): [group of 32 points][octet 0..15][point][8 channels]; sem_hid_rows() -> [P,128]
-        sem_hid = torch.empty(((R * S + 31) // 32, 16, 32, 8), device=dev, dtype=sem_in.dtype)
-    else:
-        sem_hid = torch.empty((R * S, 128), device=dev, dtype=sem_in.dtype if compact else torch.float32)
+        assert layout == 0, f"nsos_mlp_save16_layout: unknown layout {layout}"
+        sem_in = torch.empty((R * S, 320), device=dev, dtype=dt)
+        sem_hid = torch.empty((R * S, 128), device=dev, dtype=dt)
     ev = _ev_begin()
     if precision == "fp32":
         fn = _lib.lib().nsos_mlp_forward_rays_save_fold if fold else _lib.lib().nsos_mlp_forward_rays_save

@@ -232,7 +232,7 @@ def point_query(sd: Dict[str, Tensor], prefix: str, pts: Tensor, viewdirs: Optio
 
 def point_query_lp(sd: Dict[str, Tensor], prefix: str, pts: Tensor, viewdirs: Tensor, cfg: PortConfig,
                    dtype: torch.dtype, lp16: bool = False) -> Tensor:
-    """Emulation of the reduced-precision kernels (nerf-sos_amd/csrc/mlp_lp.hip, mlp_lp8.hip; lp16=True: mlp_lp16.hip), NOT of
+    """Emulation of the reduced-precision kernels (nerf-sos_amd/csrc/mlp_lp.hip; lp16=True: mlp_lp16.hip), NOT of
     the reference: everything that enters an MFMA is rounded to `dtype` (encodings, MFMA weights, activations after ReLU, the
     feature vector), products are accumulated in fp64 here (fp32 on the GPU).
       lp16=False: every bias is an MFMA operand (rounded); the sigma head uses 16-bit weights on the 16-bit activations, the

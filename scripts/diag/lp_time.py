@@ -1,4 +1,4 @@
-"""Interleaved A/B/C timing of the three 16-bit kernels (1 = lp4, 2 = lp8, 3 = lp16) on the C3/C5 fine-pass shape (diagnostic)."""
+"""Interleaved A/B timing of the two 16-bit kernels (1 = lp4, 3 = lp16) on the C3/C5 fine-pass shape (diagnostic)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -7,7 +7,7 @@ from nerf_sos_amd import _lib, ops, synthetic as syn
 dev = "cuda:0"
 R = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-KERNELS = tuple(int(c) for c in sys.argv[3]) if len(sys.argv) > 3 else (1, 2, 3)      # e.g. "3": mlp_lp16_kernel only (A/B libraries)
+KERNELS = tuple(int(c) for c in sys.argv[3]) if len(sys.argv) > 3 else (1, 3)      # e.g. "3": mlp_lp16_kernel only (A/B libraries)
 for sem, kw in ((0, dict(use_semantics=False)), (2, dict(use_semantics=True, sem_with_coord=True))):
     torch.manual_seed(0)
     net = nerf_sos_amd.NeRFNet(N_samples=64, N_importance=128, **kw).to(dev).eval()
@@ -19,7 +19,7 @@ for sem, kw in ((0, dict(use_semantics=False)), (2, dict(use_semantics=True, sem
     mac = {0: 593408, 2: 634496}[sem]
     for prec in ("fp16", "bf16"):
         pk = net.nerf_fine.packed_weights(prec)
-        best = {1: 1e9, 2: 1e9, 3: 1e9}
+        best = {1: 1e9, 3: 1e9}
         for rep in range(reps):
             for wps in KERNELS:
                 _lib.check(_lib.lib().nsos_mlp_lp_select_kernel(wps), "select")
@@ -32,6 +32,6 @@ for sem, kw in ((0, dict(use_semantics=False)), (2, dict(use_semantics=True, sem
                 ev[1].record(); torch.cuda.synchronize()
                 best[wps] = min(best[wps], ev[0].elapsed_time(ev[1]) / 40)
         tf = lambda ms: 2 * mac * R * 192 / (ms * 1e-3) / 1e12
-        print(f"sem {sem} {prec} R={R}: " + "   ".join(f"{ {1: 'lp4', 2: 'lp8', 3: 'lp16'}[k]} {best[k]:.4f} ms ({tf(best[k]):.0f} TF, {tf(best[k])/25.166:.1f} %)"
+        print(f"sem {sem} {prec} R={R}: " + "   ".join(f"{ {1: 'lp4', 3: 'lp16'}[k]} {best[k]:.4f} ms ({tf(best[k]):.0f} TF, {tf(best[k])/25.166:.1f} %)"
                                                          for k in KERNELS), flush=True)
 _lib.check(_lib.lib().nsos_mlp_lp_select_kernel(3), "select")

@@ -8,7 +8,7 @@ lib = os.path.join(ROOT, "nerf-sos_amd", "libnerf_sos_hip.so")
 ks = {k: v for k, v in chk.disassemble(lib).items() if "mlp_" in k and "pack" not in k}
 for name, ins in sorted(ks.items()):
     n = [i for i in ins if i.startswith("scratch_")]
-    if "lp8" in name or n:
+    if n:
         print(f"{len(n):4d} scratch ops, {len(ins):6d} instructions  {name}")
 pick = sys.argv[1] if len(sys.argv) > 1 else None
 if pick:

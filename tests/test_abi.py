@@ -112,16 +112,6 @@ def test_lds_ring_protocol_holds_in_the_built_code():
         limit = 0
         if "mlp_lp_kernel" in name:   # ...ELi<SEM>ELb<SAVE>E...: the training (SAVE) variant unpacks 128 words for its stores
             limit = 160 if "ELb1EEE" in name else 24   # (21 with the hardware-sine encoder)
-        if "mlp_lp8_kernel" in name:  # ...ELi<SEM>ELb<SAVE>ELb<PROF>E...  Round 3: every production instantiation is
-            # scratch-free (wave-uniform index math on the SALU, lane constants re-derived per tile, `ray` parked in LDS, the
-            # phase stamps in instantiations of their own) except the sem+coord TRAINING variant, which keeps ~7 dwords (a
-            # division constant, the save-row pointer) in scratch outside its MFMA chunks and ~40 more in the never-taken
-            # ocml sincosf branch for arguments >= 2^15
-            limit = 0
-            if "ELb1EEE" in name:               # PROF: diagnostics builds
-                limit = 80
-            elif "ELi2ELb1ELb0EEE" in name:     # sem+coord, SAVE
-                limit = 56
         if "mlp_lp16_kernel" in name:  # ...ELi<SEM>ELb<SAVE>ELb<PROF>E...  every inference instantiation scratch-free; the training
             # variants keep a few dwords around their stores and ~100 spill instructions inside the never-taken ocml sincosf blocks
             # (arguments >= 2^15) of the four encoder instances
@@ -154,6 +144,46 @@ def test_next_row_entry_points_validate_without_a_gpu():
     assert lib.nsos_app_correlation_loss(p, p, p, p, p, 2, 16, 5, 5, 2, 8, 8, 11, 0.18, 1, 0.46, 1, C.byref(one), None, p, 32, None) == -4
     with pytest.raises(RuntimeError, match="GPU tensor"):
         nerf_sos_amd.CorrelationLoss(None)(torch.zeros(2, 4, 3, 3), torch.zeros(2, 2, 8, 8), torch.zeros(2, 2))
+
+
+def test_16bit_packed_size_and_kernel_selection_without_a_gpu():
+    """K2-LP, ABI 11: the packed weights hold two streams, and the selector knows two kernels (3 = mlp_lp16_kernel, 1 = mlp_lp_kernel)."""
+    lib = _lib.lib()
+    slot = 36 * 1024
+    # [aux | mlp_lp_kernel's chunks | mlp_lp16_kernel's chunks + rgb_linear's four resident operands]: lp_chunks / lp16_chunks of csrc/lp_common.h
+    for sem, (n4, n16) in enumerate([(37, 37), (39, 39), (40, 39)]):
+        assert lib.nsos_mlp_packed_bytes_lp(sem) == 4096 + n4 * slot + n16 * slot + 4096
+    assert lib.nsos_mlp_packed_bytes_lp(3) == 0
+    prev = lib.nsos_mlp_lp_selected_kernel()
+    assert prev in (1, 3)
+    try:
+        for k in (1, 3):
+            assert lib.nsos_mlp_lp_select_kernel(k) == 0 and lib.nsos_mlp_lp_selected_kernel() == k
+            for refused in (0, 2, 4):        # 2 was the retired 32x32x16 two-waves-per-SIMD kernel: refused, and the selection survives
+                assert lib.nsos_mlp_lp_select_kernel(refused) == -3 and lib.nsos_mlp_lp_selected_kernel() == k
+            assert lib.nsos_mlp_save16_layout(1000) == (0 if k == 1 else 16 | 32)      # both matrices row-major, or both tile-major
+            assert lib.nsos_mlp_save16_layout(1 << 31) == 0                            # >= 2^31 points: the round-1 kernel
+    finally:
+        assert lib.nsos_mlp_lp_select_kernel(prev) == 0
+
+
+@pytest.mark.parametrize("value,expect", [("lp16", 3), ("lp4", 1), ("lp8", -3), ("lp", -3), ("", -3), (None, 3)],
+                         ids=["lp16", "lp4", "lp8", "lp", "empty", "unset"])
+def test_lp_kernel_environment_variable(value, expect):
+    """NSOS_LP_KERNEL accepts lp16 and lp4; anything else is NSOS_ERR_UNSUPPORTED from the selection and from the entries that ask
+    for it (here the host-only ones; never a silent run of the default), until a kernel is selected.  In a child process: the
+    variable is read once.  The child launches nothing."""
+    import subprocess
+    import sys
+    code = ("import sys; sys.path.insert(0, %r); import nerf_sos_amd; from nerf_sos_amd import _lib; lib = _lib.lib();"
+            "print(lib.nsos_mlp_lp_selected_kernel(), lib.nsos_mlp_save16_layout(1000),"
+            "      lib.nsos_mlp_lp_select_kernel(1), lib.nsos_mlp_lp_selected_kernel())" % ROOT)
+    env = {k: v for k, v in os.environ.items() if k not in ("NSOS_LP_KERNEL", "NSOS_LP_WAVES")}
+    if value is not None:
+        env["NSOS_LP_KERNEL"] = value
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True).stdout.splitlines()[-1].split()
+    layout = {3: "48", 1: "0", -3: "-3"}[expect]
+    assert out == [str(expect), layout, "0", "1"], out
 
 
 def test_split_fp16_entry_points_validate_without_a_gpu():

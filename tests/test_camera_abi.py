@@ -23,7 +23,7 @@ def test_camera_symbols_are_bound_and_the_abi_version_stands():
         assert name in _lib.SIGNATURES and hasattr(lib, name), name
         fn = getattr(lib, name)
         assert fn.restype is _lib.SIGNATURES[name][0] and list(fn.argtypes) == _lib.SIGNATURES[name][1]
-    assert lib.nsos_abi_version() == 10 == _lib.ABI_VERSION          # added entry points only: nothing existing moved
+    assert lib.nsos_abi_version() == 11 == _lib.ABI_VERSION          # the camera layer added entry points only; 11 is the two-stream 16-bit pack
 
 
 def test_camera_entry_points_validate_before_any_launch():

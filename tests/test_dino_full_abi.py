@@ -30,7 +30,7 @@ def test_symbols_declared_bound_and_exported():
     for n in NAMES:
         assert re.search(r"\b%s\(" % n, header), n
         assert n in _lib.SIGNATURES and hasattr(lib, n), n
-    assert "#define NSOS_ABI_VERSION 10" in header and _lib.ABI_VERSION == 10 == lib.nsos_abi_version()
+    assert "#define NSOS_ABI_VERSION 11" in header and _lib.ABI_VERSION == 11 == lib.nsos_abi_version()
 
 
 def expected_ws_bytes(B, h, w):

@@ -482,8 +482,8 @@ def test_full_image_chunked_eval_flow():
 # ------------------------------------------------------------------------------------------ K2-LP (reduced precision)
 @pytest.fixture
 def lp_kernel():
-    """Select one of the three 16-bit MLP kernels for a test (1 = mlp_lp_kernel, 2 = mlp_lp8_kernel, 3 = mlp_lp16_kernel, the
-    default) and restore the default afterwards."""
+    """Select one of the two 16-bit MLP kernels for a test (1 = mlp_lp_kernel, 3 = mlp_lp16_kernel, the default) and restore the
+    default afterwards."""
     lib = _lib.lib()
 
     def select(which):
@@ -498,7 +498,7 @@ def lp_kernel():
 def test_mlp_lp_vs_emulation(manifest, name, precision, tol, kernel, lp_kernel):
     """16-bit-input MFMA kernels vs their torch emulation (same roundings, fp64 accumulation): agreement is limited
     by rare 1-ulp rounding flips of 16-bit activations, far below the format's own error against fp32.  kernel 1 = the
-    round-1 kernel (mlp_lp8_kernel is pinned to it bit for bit below), 3 = mlp_lp16_kernel (16x16x32 tiles: fp32 hidden
+    round-1 kernel, 3 = mlp_lp16_kernel (16x16x32 tiles: fp32 hidden
     biases, 16-bit output heads -- its own emulation variant)."""
     lp_kernel(kernel)
     sd = ref_state(name, manifest, peaky=False)
@@ -770,9 +770,9 @@ def test_lp_training_variant(golden, manifest, precision, tol, lp_kernel):
         got = N(sd[k].grad)
         scale = np.abs(want).max() + 1e-12
         assert np.abs(got - want).max() <= tol * scale, f"{precision} grad {k}: {np.abs(got - want).max() / scale:.3e} of scale"
-    # (b) the saved operands, straight from the kernel -- of the lp4 / lp8 pair first (bit-identical to each other: the fp32
-    # operands come from the round-1 kernel, the compact ones from mlp_lp8_kernel), then of mlp_lp16_kernel (the default)
-    lp_kernel(2)
+    # (b) the saved operands, straight from the kernel -- of the round-1 kernel first (fp32 and compact), then of mlp_lp16_kernel
+    # (the default)
+    lp_kernel(1)
     mode = ops.sem_mode_of(**CFGS["semcoord"])
     R = rays.shape[1]
     near, far = torch.full((R,), tp.NEAR, device=DEV), torch.full((R,), tp.FAR, device=DEV)
@@ -789,9 +789,9 @@ def test_lp_training_variant(golden, manifest, precision, tol, lp_kernel):
                                                             rays[1].contiguous(), v, z, precision, compact=True)
     # compact: BOTH saved matrices in the 16-bit format -- sem_in's values are 16-bit anyway (identical), sem_hid is the fp32
     # accumulator's relu rounded to nearest even (what torch's own conversion gives)
-    # (the default kernel hands sem_in back tile-major -- [groups of 32 points, 20, 64, 8], include/nerf_sos_hip.h -- what its store
-    #  instructions write contiguously; ops.sem_in_rows is the [P,320] view of the same values)
-    assert sem_in_c.dtype == dt and sem_in_c.dim() == 4 and torch.equal(ops.sem_in_rows(sem_in_c, R * 64).float(), sem_in) and torch.equal(raw_c, raw)
+    # (the round-1 kernel hands both back row-major; the default kernel's are tile-major -- [groups of 32 points, 20, 64, 8],
+    #  include/nerf_sos_hip.h -- and ops.sem_in_rows is the [P,320] view of either)
+    assert sem_in_c.dtype == dt and sem_in_c.dim() == 2 and torch.equal(ops.sem_in_rows(sem_in_c, R * 64).float(), sem_in) and torch.equal(raw_c, raw)
     assert torch.equal(ops.sem_in_rows(ops.sem_in_tiled(sem_in.to(dt)), R * 64), sem_in.to(dt))
     assert sem_hid_c.dtype == dt and torch.equal(sem_hid_c, sem_hid.to(dt)) and torch.equal(sem_hid_c > 0, sem_hid.to(dt) > 0)
     W1 = mlp.semantic_linear[0].weight.detach().to(dt).double()
@@ -799,7 +799,7 @@ def test_lp_training_variant(golden, manifest, precision, tol, lp_kernel):
     hid = torch.relu(sem_in[:, :W1.shape[1]].double() @ W1.T + b1).float()
     assert (hid - sem_hid).abs().max() < 1e-4 * (1 + sem_hid.abs().max())
     # mlp_lp16_kernel: renders like its own inference variant bit for bit; its operands are self-consistent the same way (the
-    # head's hidden activations are stored as the 16-bit values the logit MFMAs consumed) and agree with the lp8 operands to the
+    # head's hidden activations are stored as the 16-bit values the logit MFMAs consumed) and agree with the round-1 kernel's operands to the
     # format's rounding (another contraction order upstream)
     lp_kernel(3)
     raw16, sem_in16, sem_hid16 = ops.mlp_forward_rays_save(net.nerf.packed_weights(precision), mode, rays[0].contiguous(),
@@ -971,8 +971,8 @@ def test_phase_profile_entries_stamp_monotonically_and_leave_results_alone(manif
 @pytest.mark.parametrize("precision", ["fp16", "bf16"])
 @pytest.mark.parametrize("name", ["sem", "semcoord"])
 def test_heads_only_repack_equals_a_full_pack(manifest, name, precision):
-    """nsos_mlp_pack_lp_heads (what a frozen-backbone training step re-packs: the semantic head's chunks of every stream + the
-    vector-ALU heads' block) into a buffer holding a full pack of OLD head weights == a fresh full pack of the new ones, byte for
+    """nsos_mlp_pack_lp_heads (what a frozen-backbone training step re-packs: the semantic head's chunks of the selected kernel's
+    stream, with the vector-ALU heads' block where that kernel reads it) into a buffer holding a full pack of OLD head weights == a fresh full pack of the new ones, byte for
     byte -- and NeRFMLP.packed_weights takes that path exactly when only semantic_linear.* is trainable."""
     net = nerf_sos_amd.NeRFNet(N_samples=64, N_importance=128, **CFGS[name]).to(DEV)
     net.load_state_dict(ref_state(name, manifest, peaky=True))
@@ -986,24 +986,24 @@ def test_heads_only_repack_equals_a_full_pack(manifest, name, precision):
                 v.add_(torch.randn_like(v) * 0.05)
     fresh = plan.run(None, precision)
     # the re-pack touches the stream of the SELECTED kernel only: per kernel, a render from the partly re-packed buffer equals the
-    # render from a fresh full pack, and after all three selections the buffer is the fresh pack byte for byte
+    # render from a fresh full pack, and after both selections the buffer is the fresh pack byte for byte
     rays = tp.synthetic_rays(64, seed=3).to(DEV)
     o, d = rays[0].contiguous(), rays[1].contiguous()
     z, v = ops.ray_setup(d, torch.full((64,), tp.NEAR, device=DEV), torch.full((64,), tp.FAR, device=DEV), 48, None)
     part = old
     try:
-        for k in (1, 2, 3):
+        for k in (1, 3):
             _lib.check(_lib.lib().nsos_mlp_lp_select_kernel(k), "select")
             assert ops.lp_selected_kernel() == k
             part = plan.run(part, precision, heads_only=True)
             assert part.data_ptr() == old.data_ptr()
             assert torch.equal(ops.mlp_forward_rays_lp(part, mlp.sem_mode, precision, o, d, v, z),
                                ops.mlp_forward_rays_lp(fresh, mlp.sem_mode, precision, o, d, v, z)), f"kernel {k}: heads-only re-pack != full pack"
-            if k < 3:
-                assert not torch.equal(part.view(torch.int32), fresh.view(torch.int32))     # the other streams still hold the old heads
+            if k == 1:
+                assert not torch.equal(part.view(torch.int32), fresh.view(torch.int32))     # the other stream still holds the old heads
     finally:
         _lib.check(_lib.lib().nsos_mlp_lp_select_kernel(3), "select")
-    assert torch.equal(part.view(torch.int32), fresh.view(torch.int32)), "heads-only re-packs of all three streams != full pack"
+    assert torch.equal(part.view(torch.int32), fresh.view(torch.int32)), "heads-only re-packs of both streams != full pack"
     # the module: frozen trunk, trainable heads -> first call full, later calls heads-only; results follow in-place updates
     for n_, p_ in net.named_parameters():
         p_.requires_grad = "semantic_linear" in n_
@@ -1014,7 +1014,7 @@ def test_heads_only_repack_equals_a_full_pack(manifest, name, precision):
     b = mlp.packed_weights(precision)
     assert not torch.equal(a.view(torch.int32), b.view(torch.int32))
     full = plan.run(None, precision)
-    # only the stream of the selected kernel is current; the others keep the old heads until the next full pack
+    # only the stream of the selected kernel is current; the other keeps the old heads until the next full pack
     assert not torch.equal(b.view(torch.int32), full.view(torch.int32))
     r_sel = ops.mlp_forward_rays_lp(b, mlp.sem_mode, precision, o, d, v, z)
     assert torch.equal(r_sel, ops.mlp_forward_rays_lp(full, mlp.sem_mode, precision, o, d, v, z))
@@ -1030,9 +1030,9 @@ def test_heads_only_repack_equals_a_full_pack(manifest, name, precision):
         _lib.check(_lib.lib().nsos_mlp_lp_select_kernel(3), "select")
     ops.mlp_forward_rays_save(full, mlp.sem_mode, o, d, v, z, precision, compact=False)      # (a full pack serves every stream)
     assert torch.equal(ops.mlp_forward_rays_lp(b, mlp.sem_mode, precision, o, d, v, z), ops.mlp_forward_rays_lp(full, mlp.sem_mode, precision, o, d, v, z))
-    # a change of the kernel selection forces a full pack (the other streams' heads would be stale)
+    # a change of the kernel selection forces a full pack (the other stream's heads would be stale)
     try:
-        _lib.check(_lib.lib().nsos_mlp_lp_select_kernel(2), "select")
+        _lib.check(_lib.lib().nsos_mlp_lp_select_kernel(1), "select")
         with torch.no_grad():
             params["semantic_linear.2.bias"].add_(1.0)
         c = mlp.packed_weights(precision)
@@ -1044,10 +1044,10 @@ def test_heads_only_repack_equals_a_full_pack(manifest, name, precision):
 # ------------------------------------------------------------------------------------------ K2-LP16 (16x16x32 tiles; the default)
 @pytest.mark.parametrize("precision", ["fp16", "bf16"])
 @pytest.mark.parametrize("name", ["nosem", "sem", "semcoord"])
-def test_lp16_ragged_counts_and_agreement_with_lp8(manifest, name, precision, lp_kernel):
+def test_lp16_ragged_counts_and_agreement_with_lp4(manifest, name, precision, lp_kernel):
     """mlp_lp16_kernel (round 4, the default 16-bit kernel) on ragged point counts (single points, partial waves, partial
     16-point column blocks, sample counts that straddle tiles): deterministic, finite, rows past the end untouched, the training
-    variant renders bit-identically to inference -- and it agrees with mlp_lp8_kernel to the 16-bit format's rounding (the two
+    variant renders bit-identically to inference -- and it agrees with mlp_lp_kernel to the 16-bit format's rounding (the two
     contract in different orders and round the output heads differently; each is held to its own emulation in
     test_mlp_lp_vs_emulation)."""
     net = nerf_sos_amd.NeRFNet(N_samples=64, N_importance=128, **CFGS[name]).to(DEV).eval()
@@ -1062,7 +1062,7 @@ def test_lp16_ragged_counts_and_agreement_with_lp8(manifest, name, precision, lp
         far = torch.full((R,), tp.FAR, device=DEV)
         v = ops.ray_setup(d, near, far, 2, None)[1]
         z = (tp.NEAR + (tp.FAR - tp.NEAR) * torch.rand(R, S, generator=torch.Generator().manual_seed(S))).sort(-1).values.to(DEV)
-        lp_kernel(2)
+        lp_kernel(1)
         ref = ops.mlp_forward_rays_lp(pk, mlp.sem_mode, precision, o, d, v, z)
         lp_kernel(3)
         out = ops.mlp_forward_rays_lp(pk, mlp.sem_mode, precision, o, d, v, z)
@@ -1079,21 +1079,23 @@ def test_lp16_ragged_counts_and_agreement_with_lp8(manifest, name, precision, lp
             assert bool((rows[:, 319] == 1).all()) and bool((rows[:, :256] >= 0).all()) and bool(torch.isfinite(hid_rows).all()) and bool((hid_rows >= 0).all())
 
 
-# ------------------------------------------------------------------------------------------ K2-LP8 (two waves per SIMD)
+# ------------------------------------------------------------------------------------------ K2-LP (round 1; the fall-back)
 @pytest.mark.parametrize("precision", ["fp16", "bf16"])
 @pytest.mark.parametrize("name", ["nosem", "sem", "semcoord"])
-def test_lp8_equals_lp4_bitwise(manifest, name, precision):
-    """mlp_lp8_kernel (8 waves x 32 points, the default 16-bit kernel of rounds 2-3) against mlp_lp_kernel (round 1:
-    4 waves x 64 points): same packed stream, same roundings, same accumulation order -> bit-identical raw, for ragged
-    point counts (partial tiles, single points), ray-mode sample counts that straddle tiles, and the training (SAVE)
-    variants' stored operands.  The round-1 kernel carries the accuracy tests against the emulation; this pins the new
-    kernel to it."""
+def test_lp4_ragged_counts_and_saved_operands(manifest, name, precision):
+    """mlp_lp_kernel (round 1: 4 waves x 64 points; the kernel behind the fp32 saved operands and launches of >= 2^31 points, and
+    the one that carries the accuracy tests against the emulation) on ragged point counts (partial tiles, single points) and
+    ray-mode sample counts that straddle tiles: deterministic and finite; the training (SAVE) variants render bit-identically to
+    inference; the compact operands come back row-major and are the fp32 ones in the 16-bit format (sem_in exactly -- its values
+    are 16-bit anyway --, sem_hid rounded to nearest even).  The selector refuses everything but its two kernels."""
     net = nerf_sos_amd.NeRFNet(N_samples=64, N_importance=128, **CFGS[name]).to(DEV).eval()
     net.load_state_dict(ref_state(name, manifest, peaky=True))
     mlp = net.nerf_fine
     pk = mlp.packed_weights(precision)
     lib = _lib.lib()
+    dt = torch.float16 if precision == "fp16" else torch.bfloat16
     try:
+        _lib.check(lib.nsos_mlp_lp_select_kernel(1), "select")
         for R, S in ((1, 1), (3, 7), (5, 64), (37, 192), (257, 33), (1024, 192)):
             rays = tp.synthetic_rays(R, seed=R).to(DEV)
             o, d = rays[0].contiguous(), rays[1].contiguous()
@@ -1101,29 +1103,23 @@ def test_lp8_equals_lp4_bitwise(manifest, name, precision):
             far = torch.full((R,), tp.FAR, device=DEV)
             v = ops.ray_setup(d, near, far, 2, None)[1]
             z = (tp.NEAR + (tp.FAR - tp.NEAR) * torch.rand(R, S, generator=torch.Generator().manual_seed(S))).sort(-1).values.to(DEV)
-            out = {}
-            for wps in (1, 2):
-                _lib.check(lib.nsos_mlp_lp_select_kernel(wps), "select")
-                out[wps] = ops.mlp_forward_rays_lp(pk, mlp.sem_mode, precision, o, d, v, z)
-                again = ops.mlp_forward_rays_lp(pk, mlp.sem_mode, precision, o, d, v, z)
-                assert torch.equal(out[wps], again), f"{wps} wave(s) per SIMD: not deterministic at R={R}, S={S}"
-            assert torch.isfinite(out[2]).all()
-            assert torch.equal(out[1], out[2]), f"R={R}, S={S}: lp8 differs from lp4 (max {float((out[1] - out[2]).abs().max()):.3e})"
+            out = ops.mlp_forward_rays_lp(pk, mlp.sem_mode, precision, o, d, v, z)
+            again = ops.mlp_forward_rays_lp(pk, mlp.sem_mode, precision, o, d, v, z)
+            assert torch.equal(out, again), f"not deterministic at R={R}, S={S}"
+            assert torch.isfinite(out).all()
             if name != "nosem":
-                for compact in (False, True):
-                    sv = {}
-                    for wps in (1, 2):
-                        _lib.check(lib.nsos_mlp_lp_select_kernel(wps), "select")
-                        sv[wps] = ops.mlp_forward_rays_save(pk, mlp.sem_mode, o, d, v, z, precision, compact=compact)
-                    assert not compact or (sv[1][1].dim() == 2 and sv[2][1].dim() == 4)       # row-major from the round-1 kernel, tile-major from lp8
-                    for a, b, what in zip(sv[1], sv[2], ("raw", "sem_in", "sem_hid")):
-                        if what == "sem_in":
-                            a, b = ops.sem_in_rows(a, R * S), ops.sem_in_rows(b, R * S)
-                        assert torch.equal(a, b), f"SAVE compact={compact} R={R} S={S}: {what} differs"
-                    assert torch.equal(sv[2][0], out[2]), "the training variant renders bit-identically to inference"
+                raw, sem_in, sem_hid = ops.mlp_forward_rays_save(pk, mlp.sem_mode, o, d, v, z, precision, compact=False)
+                raw_c, sem_in_c, sem_hid_c = ops.mlp_forward_rays_save(pk, mlp.sem_mode, o, d, v, z, precision, compact=True)
+                assert torch.equal(raw, out) and torch.equal(raw_c, out), "the training variants render bit-identically to inference"
+                assert sem_in.dtype == torch.float32 and sem_hid.dtype == torch.float32
+                assert sem_in_c.dtype == dt and sem_hid_c.dtype == dt and sem_in_c.dim() == 2 and sem_hid_c.dim() == 2      # row-major
+                assert torch.equal(sem_in_c.float(), sem_in), f"SAVE R={R} S={S}: compact sem_in differs from the fp32 one"
+                assert torch.equal(sem_hid_c, sem_hid.to(dt)), f"SAVE R={R} S={S}: compact sem_hid is not the fp32 one rounded to nearest even"
     finally:
         _lib.check(lib.nsos_mlp_lp_select_kernel(3), "select")     # the default: mlp_lp16_kernel
-    assert lib.nsos_mlp_lp_select_kernel(4) != 0 and lib.nsos_mlp_lp_select_kernel(0) != 0
+    for refused in (0, 2, 4):
+        assert lib.nsos_mlp_lp_select_kernel(refused) == -3
+    assert lib.nsos_mlp_lp_selected_kernel() == 3
 
 
 # ------------------------------------------------------------------------------------------ train-mode draws in one launch
